@@ -10,6 +10,8 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EMU = os.path.join(ROOT, "tests", "emu")
 
@@ -47,7 +49,7 @@ def _json_lines(text):
 
 
 def test_bench_two_ranks_dry_run(oracle_lib):
-    args = "--gpus 2 --steps 2 --warmup 1 --envs-per-gpu 16 --settle-frames 0 --no-cpu-baseline"
+    args = "--gpus 2 --steps 2 --warmup 1 --envs-per-gpu 16 --settle-frames 0 --full --no-cpu-baseline"
     outs = _launch(2, args)
     for rank, (rc, o, e) in enumerate(outs):
         assert rc == 0, (rank, o[-2000:], e[-4000:])
@@ -96,3 +98,31 @@ def test_a_failing_rank_ends_the_self_spawned_job(oracle_lib):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--envs-per-gpu", "16",
                         "--settle-frames", "0", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and not _json_lines(r.stdout)
+
+
+def test_plain_run_prints_the_headline_and_dumps_the_same_outputs_every_run(oracle_lib, tmp_path):
+    """A plain `bench.py --gpus 1` (emulated library): one result line with the headline keys and none of --full's figures, and
+    --dump-outputs writes the state of the last timed frame.  The frames that bring the clocks up (as many as fit in 0.5 s) start
+    from the settled state, which is put back after them, so the timed frames start from the same state in every run:
+    2 settle frames + 1 warm-up + 2 steps give the bits of 0 + 3 + 2."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(NT_EMU=EMU, NT_ROOT=ROOT, PYTHONPATH=os.pathsep.join([os.path.join(EMU, "site"), env.get("PYTHONPATH", "")]))
+
+    def run(settle, warmup, out):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", str(warmup),
+                            "--envs-per-gpu", "16", "--settle-frames", str(settle), "--dump-outputs", str(out)],
+                           env=env, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+        lines = _json_lines(r.stdout)
+        assert len(lines) == 1, r.stdout[-2000:]
+        return lines[0]
+
+    d = run(2, 1, tmp_path / "a")
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(d) and d["steps"] == 2 and d["warmup"] == 1
+    assert not {"roofline", "validity_gate", "valid_state", "cpu_baseline"} & set(d)
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 - 16 * d["config"]["substeps_per_step"]) <= 1e-6 * 16 * d["config"]["substeps_per_step"]
+    run(0, 3, tmp_path / "b")
+    for name, shape in {"body_q": (16 * 13, 7), "body_qd": (16 * 13, 6), "body_f": (16 * 13, 6), "joint_q": (16 * 19,), "joint_qd": (16 * 18,)}.items():
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all()
+        assert np.array_equal(a.view(np.int32), b.view(np.int32)), name

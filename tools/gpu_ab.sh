@@ -13,7 +13,7 @@ for e in $ENTRIES; do
   steps=$(( 4096 * 300 / envs )); [ $steps -lt 30 ] && steps=30
   echo -n "$lib cfg=${cfg:-default} envs=$envs " >> $O/${T}_ab.txt
   if [ "$lib" = product ]; then cmd="python bench.py"; else cmd="python tools/with_lib.py variants/$lib bench.py"; fi
-  ( if [ -n "${cfg:-}" ]; then export NT_XPBD_CFG=$cfg; fi; timeout 300 $cmd --no-cpu-baseline --envs-per-gpu $envs --steps $steps --warmup 20 2>&1 | grep -v amdgpu.ids | tail -1 ) | python -c "import sys,json
+  ( if [ -n "${cfg:-}" ]; then export NT_XPBD_CFG=$cfg; fi; timeout 300 $cmd --full --no-cpu-baseline --envs-per-gpu $envs --steps $steps --warmup 20 2>&1 | grep -v amdgpu.ids | tail -1 ) | python -c "import sys,json
 try:
     d=json.loads(sys.stdin.read()); print(round(d['value']/1e6,2),'M env-steps/s', round(d['roofline']['kernel_ms'],4),'ms valid',d['valid_state'], d['roofline']['kernel'])
 except Exception as e: print('FAILED', e)" >> $O/${T}_ab.txt

@@ -9,7 +9,7 @@ for e in $2; do
   for lib in $3; do
     if [ "$lib" = product ]; then cmd="python bench.py"; else cmd="python tools/with_lib.py variants/$lib bench.py"; fi
     echo -n "$w $lib " >> $O/${T}_ab.txt
-    ( timeout 900 $cmd --no-cpu-baseline --workload $w --steps $steps --warmup 3 2>&1 | grep -v amdgpu.ids | tail -1 ) | python -c "import sys,json
+    ( timeout 900 $cmd --full --no-cpu-baseline --workload $w --steps $steps --warmup 3 2>&1 | grep -v amdgpu.ids | tail -1 ) | python -c "import sys,json
 try:
     d=json.loads(sys.stdin.read()); print(round(d['value']/1e6,4),'M env-steps/s', round(d['ms_per_step'],4),'ms/step valid',d['valid_state'])
 except Exception as e: print('FAILED', e)" >> $O/${T}_ab.txt

@@ -8,6 +8,6 @@ T=r05a
 b() { ( "$@" 2>&1 | grep -v amdgpu.ids | tail -1 ); }
 ( timeout 120 variants/valu_issue.bin 2>&1 ) > $O/${T}_valu_issue.jsonl
 ( timeout 600 python -m pytest tests/test_gpu_mesh_plane_pipeline.py -m gpu -q 2>&1 | tail -8 ) > $O/${T}_gputests_mesh_plane.log
-b timeout 400 python bench.py --no-cpu-baseline > $O/${T}_bench_default.json
-b timeout 300 python bench.py --no-cpu-baseline --workload mesh_ground --steps 20 --warmup 3 > $O/${T}_bench_mesh_ground.json
+b timeout 400 python bench.py --full --no-cpu-baseline > $O/${T}_bench_default.json
+b timeout 300 python bench.py --full --no-cpu-baseline --workload mesh_ground --steps 20 --warmup 3 > $O/${T}_bench_mesh_ground.json
 echo done > $O/${T}_done

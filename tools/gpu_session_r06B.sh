@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 T=$1; LIBS=$2; TLIBS=${3:-}
 run() {  # lib envs steps
   echo -n "$1 envs=$2 " >> $O/${T}_ab.txt
-  ( timeout 400 python tools/with_lib.py variants/$1 bench.py --no-cpu-baseline --envs-per-gpu $2 --steps $3 --warmup 20 2>&1 | grep -v amdgpu.ids | tail -1 ) | python -c "import sys,json
+  ( timeout 400 python tools/with_lib.py variants/$1 bench.py --full --no-cpu-baseline --envs-per-gpu $2 --steps $3 --warmup 20 2>&1 | grep -v amdgpu.ids | tail -1 ) | python -c "import sys,json
 try:
     d=json.loads(sys.stdin.read()); print(round(d['value']/1e6,2),'M env-steps/s', round(d['ms_per_step'],4),'ms valid',d['valid_state'], d['roofline'].get('kernel',''))
 except Exception as e: print('FAILED', e)" >> $O/${T}_ab.txt

@@ -13,7 +13,7 @@ for w in quadruped:300 quadruped_convex:100 box_stack:100 quadruped_featherstone
   for lib in $LIBS; do
     if [ "$lib" = product ]; then cmd="python bench.py"; else cmd="python tools/with_lib.py variants/$lib bench.py"; fi
     echo -n "$wl $lib " >> $O/${T}_ab_workloads.txt
-    ( timeout 400 $cmd --no-cpu-baseline --workload $wl --steps $steps --warmup 10 2>&1 | grep -v amdgpu.ids | tail -1 ) | python -c "import sys,json
+    ( timeout 400 $cmd --full --no-cpu-baseline --workload $wl --steps $steps --warmup 10 2>&1 | grep -v amdgpu.ids | tail -1 ) | python -c "import sys,json
 try:
     d=json.loads(sys.stdin.read()); print(round(d['value']/1e6,3),'M env-steps/s', round(d['ms_per_step'],4),'ms/step valid',d['valid_state'])
 except Exception as e: print('FAILED', e)" >> $O/${T}_ab_workloads.txt

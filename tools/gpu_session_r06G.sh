@@ -15,7 +15,7 @@ for w in quadruped:300 sdf_bin:6; do
   for lib in libr05ship.so product libr05ship.so product; do
     if [ "$lib" = product ]; then cmd="python bench.py"; else cmd="python tools/with_lib.py variants/$lib bench.py"; fi
     echo -n "$wl $lib " >> $O/${T}_ab_workloads.txt
-    ( timeout 600 $cmd --no-cpu-baseline --workload $wl --steps $steps --warmup 4 2>&1 | grep -v amdgpu.ids | tail -1 ) | python -c "import sys,json
+    ( timeout 600 $cmd --full --no-cpu-baseline --workload $wl --steps $steps --warmup 4 2>&1 | grep -v amdgpu.ids | tail -1 ) | python -c "import sys,json
 try:
     d=json.loads(sys.stdin.read()); print(round(d['value']/1e6,4),'M env-steps/s', round(d['ms_per_step'],4),'ms/step valid',d['valid_state'], d['roofline'].get('hbm_peak_measured'))
 except Exception as e: print('FAILED', e)" >> $O/${T}_ab_workloads.txt

@@ -11,7 +11,7 @@ done
 for rep in 1 2; do for lib in $3; do
   if [ "$lib" = product ]; then cmd="python bench.py"; else cmd="python tools/with_lib.py variants/$lib bench.py"; fi
   echo -n "quadruped_featherstone $lib " >> $O/${T}_ab_featherstone.txt
-  ( timeout 600 $cmd --no-cpu-baseline --workload quadruped_featherstone --steps 200 --warmup 10 2>&1 | grep -v amdgpu.ids | tail -1 ) | python -c "import sys,json
+  ( timeout 600 $cmd --full --no-cpu-baseline --workload quadruped_featherstone --steps 200 --warmup 10 2>&1 | grep -v amdgpu.ids | tail -1 ) | python -c "import sys,json
 try:
     d=json.loads(sys.stdin.read()); print(round(d['value']/1e6,3),'M env-steps/s', round(d['ms_per_step'],4),'ms/step valid',d['valid_state'])
 except Exception as e: print('FAILED', e)" >> $O/${T}_ab_featherstone.txt

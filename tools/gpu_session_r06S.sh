@@ -13,15 +13,15 @@ if want pmc; then
   rm -rf $O/pmc_quadruped_* $O/pmc_sq_quadruped_4096 $O/pmc_quadruped_featherstone_*
 fi
 if want bench; then
-  b timeout 600 python bench.py > $O/${T}_bench_default.json
-  b timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/${T}_bench_driver_shape.json
-  b timeout 900 python bench.py --no-cpu-baseline --steps 200 --warmup 20 --sweep 4096,8192,65536 --sweep-out $O/${T}_env_sweep.json > $O/${T}_env_sweep.log
+  b timeout 600 python bench.py --full > $O/${T}_bench_default.json
+  b timeout 300 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > $O/${T}_bench_driver_shape.json
+  b timeout 900 python bench.py --full --no-cpu-baseline --steps 200 --warmup 20 --sweep 4096,8192,65536 --sweep-out $O/${T}_env_sweep.json > $O/${T}_env_sweep.log
 fi
 if want prof; then
   cd /tmp
-  timeout 600 rocprofv3 --kernel-trace --stats -d $O/${T}_prof_q -o p --output-format csv -- python $R/bench.py --no-cpu-baseline --steps 1500 --warmup 100 > $O/${T}_prof_q.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats -d $O/${T}_prof_q -o p --output-format csv -- python $R/bench.py --full --no-cpu-baseline --steps 1500 --warmup 100 > $O/${T}_prof_q.log 2>&1
   f=$(find $O/${T}_prof_q -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && head -8 "$f" > $O/${T}_kernel_stats_quadruped.csv; rm -rf $O/${T}_prof_q
-  timeout 600 rocprofv3 --kernel-trace --stats -d $O/${T}_prof_f -o p --output-format csv -- python $R/bench.py --no-cpu-baseline --workload quadruped_featherstone --steps 400 --warmup 40 > $O/${T}_prof_f.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats -d $O/${T}_prof_f -o p --output-format csv -- python $R/bench.py --full --no-cpu-baseline --workload quadruped_featherstone --steps 400 --warmup 40 > $O/${T}_prof_f.log 2>&1
   f=$(find $O/${T}_prof_f -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && head -8 "$f" > $O/${T}_kernel_stats_featherstone.csv; rm -rf $O/${T}_prof_f
   cd $R
 fi
@@ -32,7 +32,7 @@ fi
 if want secondary; then
   for w in quadruped_convex:100 box_stack:100 quadruped_featherstone:100 quadruped_api:40 hull_bin:10 sdf_bin:6 mesh_ground:20 hydro_bin:2; do
     IFS=: read wl steps <<< "$w"
-    b timeout 900 python bench.py --no-cpu-baseline --workload $wl --steps $steps --warmup 4 > $O/${T}_bench_$wl.json
+    b timeout 900 python bench.py --full --no-cpu-baseline --workload $wl --steps $steps --warmup 4 > $O/${T}_bench_$wl.json
   done
 fi
 echo done > $O/${T}_done_$P

@@ -8,6 +8,6 @@ T=${1:-r06U}
 b() { ( "$@" 2>&1 | grep -v amdgpu.ids | tail -1 ); }
 ( timeout 1500 python -m pytest tests/test_gpu_sdf_pipeline.py tests/test_gpu_hydro_bands.py tests/test_gpu_hydro_forces.py tests/test_gpu_hydro_stack.py tests/test_gpu_sdf.py tests/test_gpu_parity_featherstone.py -m gpu -q -p no:cacheprovider 2>&1 | tail -12 ) > $O/${T}_gputests.log
 bash tools/gpu_session_r06Q.sh $T product
-b timeout 600 python bench.py --no-cpu-baseline --workload hydro_bin --steps 2 --warmup 4 > $O/${T}_bench_hydro_bin.json
-b timeout 600 python bench.py --no-cpu-baseline --workload quadruped_featherstone --steps 100 --warmup 4 > $O/${T}_bench_quadruped_featherstone.json
+b timeout 600 python bench.py --full --no-cpu-baseline --workload hydro_bin --steps 2 --warmup 4 > $O/${T}_bench_hydro_bin.json
+b timeout 600 python bench.py --full --no-cpu-baseline --workload quadruped_featherstone --steps 100 --warmup 4 > $O/${T}_bench_quadruped_featherstone.json
 echo done > $O/${T}_done

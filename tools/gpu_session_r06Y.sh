@@ -9,7 +9,7 @@ T=${1:-r06Y}
 bash tools/gpu_ab_generic.sh $T "hydro_bin:2 sdf_bin:6" "product libsdf_prev.so product libsdf_prev.so"
 bash tools/gpu_session_r06Q.sh $T product
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/${T}_prof_s -o p --output-format csv -- python $R/bench.py --no-cpu-baseline --workload sdf_bin --steps 2 --warmup 2 > $O/${T}_prof_sdf.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/${T}_prof_s -o p --output-format csv -- python $R/bench.py --full --no-cpu-baseline --workload sdf_bin --steps 2 --warmup 2 > $O/${T}_prof_sdf.log 2>&1
 f=$(find $O/${T}_prof_s -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && head -12 "$f" | cut -d, -f1-4 | cut -c1-150 > $O/${T}_kernel_stats_sdf_bin.csv; rm -rf $O/${T}_prof_s
 cd $R
 echo done > $O/${T}_done

@@ -6,7 +6,7 @@ R=$PWD; O=$R/gpurun_out/pcs_$M; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
 if [ "$M" = stochastic ]; then U="--pc-sampling-unit cycles --pc-sampling-interval 1048576"; else U="--pc-sampling-unit time --pc-sampling-interval 1"; fi
 timeout 240 rocprofv3 --pc-sampling-beta-enabled --pc-sampling-method $M $U -d $O -o pcs --output-format csv -- \
-  python $R/bench.py --steps 200 --warmup 20 --no-cpu-baseline > $O/run.log 2>&1
+  python $R/bench.py --steps 200 --warmup 20 --full --no-cpu-baseline > $O/run.log 2>&1
 echo rc=$? >> $O/run.log
 find $O -type f | head -20
 for f in $(find $O -name "*.csv"); do echo == $f; wc -l $f; head -3 $f | cut -c1-300; done
