@@ -1,0 +1,107 @@
+/* newton_hip_contacts.h -- the key-ordered contact export and the frame-to-frame matching report of libnewton_hip.so on the device
+ * (extension of newton_hip.h).
+ *
+ * Reference interface replaced (paths relative to the Newton source tree):
+ *   ContactSorter             newton/_src/geometry/contact_sort.py:194-440   the deterministic mode of CollisionPipeline.collide: the
+ *                                                                            flat contact arrays ordered by the contact sort key
+ *   ContactMatcher report     newton/_src/geometry/contact_match.py:602-1055 rigid_contact_match_index in the sorted order, the
+ *                                                                            new / broken lists (collide.py:1126-1129,2033-2135)
+ *
+ * The order is a stable sort on the 64-bit key (shape0 << 32 | shape1) over the raw export order of nt_contacts_export followed by
+ * the live rows of nt_contacts.flat (every env's analytic slots, every env's convex slots, then the rows).  No comparison sort runs:
+ * the (shape0, shape1) pairs that can carry a contact are fixed when the pipeline is built, so every (pair, orientation) gets a
+ * BUCKET whose rank in key order is computed once on the host (nt_contact_order).  Per export: live contacts per bucket -> a
+ * multi-block exclusive scan over the ranked buckets (no atomics on the counts, no host read) -> every live slot / row scattered to
+ * its position; inside a bucket the raw order is kept.
+ *
+ * Same conventions as newton_hip.h: device pointers owned by the caller, work enqueued on `stream`, no allocation, no
+ * synchronisation -- every entry point can be recorded by nt_graph_capture_begin / _end. */
+#ifndef NEWTON_HIP_CONTACTS_H
+#define NEWTON_HIP_CONTACTS_H
+
+#include "newton_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* The order table.  Buckets: tile bucket (pair p, env e, orientation o) for every device pair of every env, o = 0 when the slot
+ * carries shape0 == tile_shape0[p][e], else 1 (the pair written the other way round); row bucket (world w, j) for the K keys a
+ * world's rows may carry (both orientations of every pair the SDF legs may route in that world; row_key ascending per world).
+ * Ranks: enumerate the buckets in raw order -- tile buckets of the analytic pairs (env-major, then pair, then orientation), those of
+ * the convex pairs likewise, then the row buckets world-major -- and take the inverse of a STABLE argsort of their keys (buckets
+ * of equal keys then keep the raw order of their contacts).  Scratch sizes: B = 2 * env_count * np + env_count * K buckets. */
+typedef struct {
+    int32_t bucket_count;         /* B */
+    const int32_t* tile_shape0;   /* [np][env_count] Newton id that orientation 0 of (pair, env) writes as shape0 */
+    const int32_t* tile_rank;     /* [np][env_count][2] rank of the tile bucket */
+    int32_t row_keys;             /* K (0: no row buckets) */
+    const int64_t* row_key;       /* [env_count][K] shape0 << 32 | shape1, ascending inside a world */
+    const int32_t* row_rank;      /* [env_count][K] rank of the row bucket */
+    int32_t* bucket_fill;         /* [B] scratch: live contacts per bucket, indexed by rank */
+    int32_t* bucket_start;        /* [B] scratch: exclusive scan of bucket_fill */
+    int32_t* block_sum;           /* [B / 1024 + 2] scratch of the scan */
+    int32_t* row_bucket;          /* [row_capacity] scratch: rank of the row's bucket, -1 inert */
+    int32_t* row_sub;             /* [row_capacity] scratch: position of the row inside its bucket */
+    int32_t* row_unmatched;       /* [1]: rows whose (shape0, shape1) is in no bucket of their world (never set by this project's
+                                   * legs; such rows are left out of the export), accumulated -- zero it to re-arm */
+} nt_contact_order;
+
+/* Key-ordered flat arrays (Newton's Contacts layout, AoS).  Entries at or beyond count: shape ids -1, floats 0. */
+typedef struct {
+    int32_t cap;                  /* capacity of the flat arrays (Contacts.rigid_contact_max) */
+    int32_t row_capacity;         /* capacity of nt_contacts.flat (0: no rows) */
+    int32_t* count;               /* [1] rigid_contact_count */
+    int32_t* shape0;              /* [cap] */
+    int32_t* shape1;
+    float* point0;                /* [cap][3] */
+    float* point1;
+    float* offset0;
+    float* offset1;
+    float* normal;
+    float* margin0;               /* [cap] */
+    float* margin1;
+    float* stiffness;             /* [cap] or NULL: nt_contacts.prop of the slots, nt_flat_rows.stiffness of the rows (0 when the */
+    float* damping;               /* source has none) -- Contacts.rigid_contact_stiffness / _damping / _friction */
+    float* friction;
+    int32_t* slot_flat;           /* [np*cpp][ES] out: position of every live slot in the arrays, -1 otherwise */
+    int32_t* row_flat;            /* [row_capacity] out: position of every live row, -1 otherwise */
+} nt_sorted_contacts;
+
+/* counts -> scan -> scatter -> tail fill; writes every entry of `out` */
+nt_status nt_contacts_export_sorted(const nt_model* m, const nt_contacts* c, const nt_contact_order* o, nt_sorted_contacts* out,
+                                    void* stream);
+
+/* The matching report in the sorted order.  The previous frame is described by what nt_contacts_order_save left (positions of its
+ * slots and rows, its count) and by the matchers' histories (nt_contact_history / nt_flat_history, before their save). */
+typedef struct {
+    int32_t* prev_slot_flat;        /* [np*cpp][ES] positions of the previous frame's slots (initialise to -1) */
+    int32_t* prev_row_flat;         /* [row_capacity] or NULL without rows (initialise to -1) */
+    int32_t* prev_count;            /* [1] the previous frame's count (0 = no previous frame) */
+    const int32_t* slot_match;      /* [np*cpp][ES] nt_contacts_match: previous SLOT, -1 or -2 */
+    const int32_t* row_match;       /* [row_capacity] nt_flat_rows_match: previous ROW, -1 or -2; NULL without rows */
+    const uint8_t* prev_slot_live;  /* nt_contact_history.prev_live (zeroed for reset worlds) */
+    const uint8_t* prev_row_live;   /* nt_flat_history.prev_live, prev_row_start, prev_pair_count (a world with */
+    const int32_t* prev_row_start;  /* prev_pair_count 0 was reset); NULL without rows */
+    const int32_t* prev_pair_count;
+    uint8_t* reset_world_mask;      /* [env_count] or NULL: the mask nt_contacts_match consumed; cleared by nt_contacts_order_save */
+    int32_t* match_index;           /* [cap] out: rigid_contact_match_index (-1 beyond the count) */
+    int32_t* new_indices;           /* [cap] out or NULL (no report): ascending positions i < count with match_index[i] < 0 */
+    int32_t* new_count;             /* [1] */
+    int32_t* broken_indices;        /* [cap] out: ascending positions of the previous frame's live contacts that no contact matched */
+    int32_t* broken_count;          /* [1] */
+    int32_t* flag;                  /* [cap] scratch */
+    int32_t* offset;                /* [cap] scratch */
+    int32_t* block_sum;             /* [cap / 1024 + 2] scratch */
+} nt_contact_report;
+
+/* match_index (+ the new / broken lists when new_indices is set) of the frame `sorted` holds; call after nt_contacts_match /
+ * nt_flat_rows_match (and the sticky replay) and nt_contacts_export_sorted, before the histories are saved */
+nt_status nt_contacts_match_report(const nt_model* m, const nt_sorted_contacts* sorted, const nt_contact_report* r, void* stream);
+/* the frame as the next frame's previous one: positions, count; clears reset_world_mask */
+nt_status nt_contacts_order_save(const nt_model* m, const nt_sorted_contacts* sorted, const nt_contact_report* r, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

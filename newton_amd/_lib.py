@@ -1,4 +1,5 @@
-"""ctypes binding of libnewton_hip.so (the C ABI declared in include/newton_hip.h, include/newton_hip_broadphase.h and include/newton_hip_mesh.h).
+"""ctypes binding of libnewton_hip.so (the C ABI declared in include/newton_hip.h, include/newton_hip_broadphase.h, include/newton_hip_mesh.h
+and include/newton_hip_contacts.h).
 
 The product path has NO CPU fallback: if the shared library is missing or cannot be loaded, every
 solver / collision entry point raises.  Build it with ``python -c "import __graft_entry__ as g; g.build()"``.
@@ -208,6 +209,30 @@ class nt_contact_history(C.Structure):
                 ("prev_body_frame", C.c_void_p)]
 
 
+class nt_contact_order(C.Structure):
+    """include/newton_hip_contacts.h: bucket ranks of the key-ordered export + its scratch."""
+    _fields_ = [("bucket_count", C.c_int32), ("tile_shape0", C.c_void_p), ("tile_rank", C.c_void_p), ("row_keys", C.c_int32),
+                ("row_key", C.c_void_p), ("row_rank", C.c_void_p), ("bucket_fill", C.c_void_p), ("bucket_start", C.c_void_p),
+                ("block_sum", C.c_void_p), ("row_bucket", C.c_void_p), ("row_sub", C.c_void_p), ("row_unmatched", C.c_void_p)]
+
+
+class nt_sorted_contacts(C.Structure):
+    """include/newton_hip_contacts.h: the key-ordered flat arrays."""
+    _fields_ = [("cap", C.c_int32), ("row_capacity", C.c_int32), ("count", C.c_void_p), ("shape0", C.c_void_p), ("shape1", C.c_void_p),
+                ("point0", C.c_void_p), ("point1", C.c_void_p), ("offset0", C.c_void_p), ("offset1", C.c_void_p), ("normal", C.c_void_p),
+                ("margin0", C.c_void_p), ("margin1", C.c_void_p), ("stiffness", C.c_void_p), ("damping", C.c_void_p),
+                ("friction", C.c_void_p), ("slot_flat", C.c_void_p), ("row_flat", C.c_void_p)]
+
+
+class nt_contact_report(C.Structure):
+    """include/newton_hip_contacts.h: matching report in the sorted order."""
+    _fields_ = [("prev_slot_flat", C.c_void_p), ("prev_row_flat", C.c_void_p), ("prev_count", C.c_void_p), ("slot_match", C.c_void_p),
+                ("row_match", C.c_void_p), ("prev_slot_live", C.c_void_p), ("prev_row_live", C.c_void_p), ("prev_row_start", C.c_void_p),
+                ("prev_pair_count", C.c_void_p), ("reset_world_mask", C.c_void_p), ("match_index", C.c_void_p), ("new_indices", C.c_void_p),
+                ("new_count", C.c_void_p), ("broken_indices", C.c_void_p), ("broken_count", C.c_void_p), ("flag", C.c_void_p),
+                ("offset", C.c_void_p), ("block_sum", C.c_void_p)]
+
+
 class nt_hydro_args(C.Structure):
     _fields_ = [("pairs", C.c_void_p), ("pair_count", C.c_int32), ("shape_transform", C.c_void_p), ("shape_data", C.c_void_p),
                 ("shape_gap", C.c_void_p), ("shape_kh", C.c_void_p), ("shape_sdf_index", C.c_void_p), ("sdf_table", C.c_void_p),
@@ -385,6 +410,11 @@ SYMBOLS = {
                                    C.POINTER(nt_contact_history), C.c_void_p, _P]),
     "nt_contacts_save_history": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_state), C.POINTER(nt_contacts),
                                               C.POINTER(nt_contact_history), _P]),
+    # include/newton_hip_contacts.h
+    "nt_contacts_export_sorted": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_contacts), C.POINTER(nt_contact_order),
+                                              C.POINTER(nt_sorted_contacts), _P]),
+    "nt_contacts_match_report": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_sorted_contacts), C.POINTER(nt_contact_report), _P]),
+    "nt_contacts_order_save": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_sorted_contacts), C.POINTER(nt_contact_report), _P]),
     "nt_hydro_collide": (C.c_int32, [C.POINTER(nt_hydro_args), _P]),
     "nt_hydro_pairs": (C.c_int32, [C.POINTER(nt_hydro_args), _P]),
     "nt_sdf_candidate_pairs": (C.c_int32, [C.POINTER(nt_sdf_scene), _P, _P, _P, _P, _P, _P]),

@@ -3,7 +3,9 @@
 ``CollisionPipeline.collide(state, contacts)`` runs the gfx950 collide kernel (AABBs -> broad phase ->
 narrow phase -> contact writer) through the C ABI ``nt_collide``.  Contacts live in fixed per-env slots
 (slot = pair * cpp + k, env-major SoA); the Newton-shaped flat arrays (``rigid_contact_shape0`` ...,
-in the reference's append order) are produced on read by ``nt_contacts_export``.
+in the reference's append order) are produced on read by ``nt_contacts_export``.  With ``deterministic=True`` (or contact
+matching) they are ordered by the contact key on the device (``nt_contacts_export_sorted``, include/newton_hip_contacts.h) into
+persistent buffers, and the matching report is built there too: such a ``collide()`` reads nothing back and records into a hipGraph.
 """
 from __future__ import annotations
 
@@ -22,6 +24,53 @@ def _torch():
     import torch  # noqa: PLC0415
 
     return torch
+
+
+def _newton_ids(t, local, world):
+    """Newton shape ids of template shapes `local` (0..ns-1 env-local, ns.. global) in worlds `world` (broadcast)."""
+    local, world = np.broadcast_arrays(np.asarray(local, np.int64), np.asarray(world, np.int64))
+    glob = np.asarray(t.gshape_id, np.int64)
+    g = glob[np.clip(local - t.ns, 0, max(len(glob) - 1, 0))] if len(glob) else np.zeros_like(local)
+    return np.where(local < t.ns, t.shape_local0 + world * t.ns + local, g)
+
+
+def contact_order_tables(model):
+    """Host tables of the key-ordered export (nt_contact_order, include/newton_hip_contacts.h), built once per model: the orientation-0
+    shape0 of every (device pair, env), the row keys of every world (both orientations of every pair the SDF legs may route) and the
+    rank of every bucket -- the inverse of one stable argsort of the bucket keys enumerated in the raw export order."""
+    cached = getattr(model, "_contact_order_tables", None)
+    if cached is not None:
+        return cached
+    t = model.env
+    E, P, npa = t.env_count, t.np, t.np_analytic
+    w = np.arange(E)[None, :]
+    pa, pb = np.asarray(t.pair_a, np.int64)[:, None], np.asarray(t.pair_b, np.int64)[:, None]
+    ty = np.asarray(t.tile_shape_type, np.int64)
+    swap = ty[pa] > ty[pb] if P else np.zeros((0, 1), bool)  # the tile writes its contacts type-sorted (nt_match.hip midpoint)
+    a, b = _newton_ids(t, np.where(swap, pb, pa), w), _newton_ids(t, np.where(swap, pa, pb), w)  # [P, E]
+    tile_key = np.stack([(a << 32) + b, (b << 32) + a], axis=-1)  # [P, E, 2]
+    ids = np.arange(P * E * 2).reshape(P, E, 2)
+    keys, tile_ids = [], []
+    for lo, hi in ((0, npa), (npa, P)):  # raw order: every env's analytic slots, then every env's convex slots
+        keys.append(tile_key[lo:hi].transpose(1, 0, 2).reshape(-1))
+        tile_ids.append(ids[lo:hi].transpose(1, 0, 2).reshape(-1))
+    sp = np.asarray(getattr(t, "sdf_pair", np.zeros((0, 2))), np.int64).reshape(-1, 2)
+    K = 2 * len(sp)
+    row_key = np.zeros((E, 0), np.int64)
+    if K:
+        ra, rb = _newton_ids(t, sp[:, 0][None, :], w.T), _newton_ids(t, sp[:, 1][None, :], w.T)  # [E, T]
+        row_key = np.sort(np.concatenate([(ra << 32) + rb, (rb << 32) + ra], axis=1), axis=1)
+        keys.append(row_key.reshape(-1))
+    keys = np.concatenate(keys) if keys else np.zeros(0, np.int64)
+    rank = np.empty(len(keys), np.int64)
+    rank[np.argsort(keys, kind="stable")] = np.arange(len(keys))
+    n_tile = P * E * 2
+    tile_rank = np.empty(n_tile, np.int64)
+    tile_rank[np.concatenate(tile_ids)] = rank[:n_tile]
+    out = {"bucket_count": len(keys), "tile_shape0": a.astype(np.int32), "tile_rank": tile_rank.astype(np.int32),
+           "row_keys": K, "row_key": row_key, "row_rank": rank[n_tile:].reshape(E, K).astype(np.int32)}
+    model._contact_order_tables = out
+    return out
 
 
 class Contacts:
@@ -75,6 +124,9 @@ class Contacts:
         self._export = None
         self._generation = 0
         self._export_generation = -1
+        self._raw_rows, self._order_cache = None, None
+        if self.sort_by_key:
+            self._init_sorted_export()
         # extended attribute (contacts.py:170-226): [rigid_contact_max, 6] force / torque on shape0's body, filled by
         # solver.update_contacts(); _impulse holds the solver's per-slot accumulated impulses of the last step
         self.force = None
@@ -127,6 +179,8 @@ class Contacts:
     def _exported(self):
         if self._export is not None and self._export_generation == self._generation:
             return self._export
+        if self.sort_by_key:
+            return self._export_sorted()
         torch = _torch()
         dm = self.model.device_model()
         cap = max(self.rigid_contact_max, 1)
@@ -173,28 +227,112 @@ class Contacts:
                 e["damping"][n0:n0 + k] = f.damping[live]
                 e["friction"][n0:n0 + k] = f.friction_scale[live]
             e["count"][0] = n0 + k
-            self._flat_live, self._flat_n0 = live, n0
-        self._sort_order = None
-        if self.sort_by_key:
-            n = min(int(e["count"].item()), cap)
-            if n > 1:
-                # a pair's contacts are exported consecutively in sub-contact order, so a stable sort on (shape0, shape1)
-                # is the sort on the full key; 32 bits per id (the reference packs 20: contact_data.py:60-90, which
-                # aliases beyond 2^20 shapes)
-                key = e["shape0"][:n].to(torch.int64) * (1 << 32) + e["shape1"][:n].to(torch.int64)
-                order = torch.sort(key, stable=True).indices
-                for k, v in e.items():
-                    if k != "count":
-                        v[:n] = v[:n][order]
-                self._sort_order = order  # SolverXPBD.update_contacts applies the same permutation to Contacts.force
+            self._raw_rows = (live, n0, self._generation)
         self._export, self._export_generation = e, self._generation
         return e
 
+    # -- key-ordered views (sort_by_key): persistent buffers written by nt_contacts_export_sorted --------------------------------------
+    def _init_sorted_export(self):
+        """Allocate the key-ordered flat arrays, the slot / row positions and the order table once.  The order is a stable sort on
+        (shape0 << 32 | shape1) over the raw append order -- a pair's contacts are exported consecutively in sub-contact order, so
+        this is the sort on the reference's full key (contact_data.py:60-90, 32 bits per id instead of its 20)."""
+        torch = _torch()
+        dm, t = self.model.device_model(), self.model.env
+        dev, cap = dm.device, max(self.rigid_contact_max, 1)
+        i32, f32 = torch.int32, torch.float32
+        e = {"count": torch.zeros(1, dtype=i32, device=dev),
+             "shape0": torch.full((cap,), -1, dtype=i32, device=dev), "shape1": torch.full((cap,), -1, dtype=i32, device=dev)}
+        for name in ("point0", "point1", "offset0", "offset1", "normal"):
+            e[name] = torch.zeros((cap, 3), dtype=f32, device=dev)
+        e["margin0"], e["margin1"] = torch.zeros(cap, dtype=f32, device=dev), torch.zeros(cap, dtype=f32, device=dev)
+        if self._prop is not None or (self._flat is not None and self._flat.stiffness is not None):
+            for name in ("stiffness", "damping", "friction"):
+                e[name] = torch.zeros(cap, dtype=f32, device=dev)
+        self._export = e
+        row_cap = self._flat.capacity if self._flat is not None else 0
+        self._slot_flat = torch.full((max(self._slots, 1), t.env_stride), -1, dtype=i32, device=dev)
+        self._row_flat = torch.full((max(row_cap, 1),), -1, dtype=i32, device=dev)
+        tab = contact_order_tables(self.model)
+        K = tab["row_keys"] if row_cap else 0
+        B = 2 * t.env_count * t.np + t.env_count * K
+
+        def up(a, dtype):
+            a = np.ascontiguousarray(a)
+            return torch.from_numpy(a if a.size else np.zeros(1, a.dtype)).to(device=dev, dtype=dtype)
+
+        self._order_tabs = (up(tab["tile_shape0"], i32), up(tab["tile_rank"], i32), up(tab["row_key"], torch.int64),
+                            up(tab["row_rank"], i32))
+        self._order_scratch = (torch.zeros(max(B, 1), dtype=i32, device=dev), torch.zeros(max(B, 1), dtype=i32, device=dev),
+                               torch.zeros(B // 1024 + 2, dtype=i32, device=dev), torch.zeros(max(row_cap, 1), dtype=i32, device=dev),
+                               torch.zeros(max(row_cap, 1), dtype=i32, device=dev))
+        self.order_unmatched_rows = torch.zeros(1, dtype=i32, device=dev)  # rows outside every bucket (stays 0: every leg's pairs have one)
+        o = _lib.nt_contact_order()
+        o.bucket_count, o.row_keys = B, K
+        o.tile_shape0, o.tile_rank, o.row_key, o.row_rank = (x.data_ptr() for x in self._order_tabs)
+        o.bucket_fill, o.bucket_start, o.block_sum, o.row_bucket, o.row_sub = (x.data_ptr() for x in self._order_scratch)
+        o.row_unmatched = self.order_unmatched_rows.data_ptr()
+        self._order = o
+        so = _lib.nt_sorted_contacts()
+        so.cap, so.row_capacity = cap, row_cap
+        for name, v in e.items():
+            setattr(so, name, v.data_ptr())
+        so.slot_flat, so.row_flat = self._slot_flat.data_ptr(), self._row_flat.data_ptr()
+        self._sorted = so
+
+    def _export_sorted(self):
+        """(Re)write the key-ordered views from the slots and rows: device work only, no host read, no allocation."""
+        dm = self.model.device_model()
+        _lib.check(dm.lib.nt_contacts_export_sorted(C.byref(dm.desc), C.byref(self._desc()), C.byref(self._order),
+                                                    C.byref(self._sorted), dm.stream()), "nt_contacts_export_sorted")
+        self._export_generation = self._generation
+        return self._export
+
+    def _raw_row_layout(self):
+        """(live rows of the SDF legs in row order, number of slot contacts before them) of the raw append order."""
+        if self._raw_rows is None or self._raw_rows[2] != self._generation:
+            if not self.sort_by_key:
+                self._exported()
+            else:  # a query: reads the counts back
+                torch = _torch()
+                t, f = self.model.env, self._flat
+                n0 = min(int((self._shape0[: self._slots, : t.env_count] >= 0).sum().item()), self._slot_contact_max)
+                if f is None:
+                    return (None, n0, self._generation)
+                nf = min(int(f.row_start[-1].item()), f.capacity)
+                self._raw_rows = (torch.nonzero(f.shape0[:nf] != f.shape1[:nf]).flatten(), n0, self._generation)
+        return self._raw_rows
+
+    _flat_live = property(lambda self: self._raw_row_layout()[0])
+    _flat_n0 = property(lambda self: self._raw_row_layout()[1])
+
     def export_order(self):
         """Permutation from the raw append order to the order of the rigid_contact_* arrays (None = identity): row i of the
-        flat arrays is raw row export_order()[i].  Non-trivial only with CollisionPipeline(deterministic=True)."""
-        self._exported()
-        return self._sort_order
+        flat arrays is raw row export_order()[i].  Non-trivial only with CollisionPipeline(deterministic=True).  (A query: it
+        reads the count back.)"""
+        e = self._exported()
+        if not self.sort_by_key:
+            return None
+        if self._order_cache is not None and self._order_cache[1] == self._generation:
+            return self._order_cache[0]
+        torch = _torch()
+        t = self.model.env
+        n = min(int(e["count"].item()), max(self.rigid_contact_max, 1))
+        order = None
+        if n > 1:  # (the raw index of every slot / row, scattered to its sorted position)
+            order = torch.empty(n, dtype=torch.int64, device=e["count"].device)
+            E, nas, ncs = t.env_count, t.np_analytic * t.cpp, self._slots
+            base = 0
+            for lo, hi in ((0, nas), (nas, ncs)):
+                pos = self._slot_flat[lo:hi, :E].T.reshape(-1)
+                pos = pos[pos >= 0].to(torch.int64)
+                order[pos] = base + torch.arange(pos.numel(), device=pos.device)
+                base += int(pos.numel())
+            if self._flat is not None:
+                pos = self._row_flat[: self._flat.capacity]
+                pos = pos[pos >= 0].to(torch.int64)
+                order[pos] = base + torch.arange(pos.numel(), device=pos.device)
+        self._order_cache = (order, self._generation)
+        return order
 
     rigid_contact_count = property(lambda self: self._exported()["count"])
     rigid_contact_shape0 = property(lambda self: self._exported()["shape0"])
@@ -271,6 +409,13 @@ class ContactMatcher:
         self._match = torch.full((ns, t.env_stride), -1, dtype=torch.int32, device=dev)
         self._prev_flat = None  # flat (export-order) index of every previous slot
         self._reset_mask = None
+        # key-ordered contacts (Contacts.sort_by_key) take the device path: the mask of the worlds reset since the last match (consumed
+        # by nt_contacts_match, cleared by nt_contacts_order_save), the previous frame's positions of its slots / rows and its count
+        i32 = torch.int32
+        self._reset_buf = torch.zeros(t.env_stride, dtype=torch.uint8, device=dev)
+        self._prev_slot_flat = torch.full((ns, t.env_stride), -1, dtype=i32, device=dev)
+        self._prev_row_flat = torch.full((sdf_leg.row_capacity,), -1, dtype=i32, device=dev) if sdf_leg is not None else None
+        self._prev_count = torch.zeros(1, dtype=i32, device=dev)
         h = _lib.nt_contact_history()
         h.prev_pos_world, h.prev_normal, h.prev_live = self._pos.data_ptr(), self._normal.data_ptr(), self._live.data_ptr()
         self.sticky = bool(sticky)
@@ -288,9 +433,12 @@ class ContactMatcher:
         if world_mask is None:
             self._live.zero_()
             self._reset_mask = None
+            self._reset_buf.zero_()
+            self._prev_count.zero_()
         else:
             m = torch.as_tensor(world_mask, device=self.dm.device).to(torch.uint8)[: t.env_count].contiguous()
             self._reset_mask = m
+            self._reset_buf[: t.env_count] |= m
             self._live[:, : t.env_count] *= (1 - m)[None, :]
 
     def previous_rows_alive(self, n: int):
@@ -321,10 +469,62 @@ class ContactMatcher:
             base += int(part.sum().item())
         return out
 
+    # -- device path (key-ordered contacts): match kernels -> [sticky replay] -> export -> report -> save, no host read ---------------
+    def _match_kernels(self, state, contacts):
+        """nt_contacts_match on the slots (previous SLOT per slot) and nt_flat_rows_match on the rows (previous ROW per row)."""
+        dm, t = self.dm, self.model.env
+        if t.np * t.cpp > 0:
+            _lib.check(dm.lib.nt_contacts_match(C.byref(dm.desc), C.byref(state._desc()), C.byref(contacts._desc()), C.byref(self._h),
+                                                self.pos_threshold, self.normal_dot_threshold, self._reset_buf.data_ptr(),
+                                                self._match.data_ptr(), dm.stream()), "nt_contacts_match")
+        self._reset_mask = None
+        if self._rows is not None:
+            self._rows.match(state, contacts._flat, self.pos_threshold, self.normal_dot_threshold)
+
+    def _report_desc(self, match_index=None, report=None) -> _lib.nt_contact_report:
+        r = _lib.nt_contact_report()
+        r.prev_slot_flat, r.prev_count, r.slot_match = self._prev_slot_flat.data_ptr(), self._prev_count.data_ptr(), self._match.data_ptr()
+        r.prev_slot_live, r.reset_world_mask = self._live.data_ptr(), self._reset_buf.data_ptr()
+        if self._rows is not None:
+            rm = self._rows
+            r.prev_row_flat, r.row_match = self._prev_row_flat.data_ptr(), rm.match_index.data_ptr()
+            r.prev_row_live, r.prev_row_start, r.prev_pair_count = (rm.prev_live.data_ptr(), rm.prev_row_start.data_ptr(),
+                                                                    rm.prev_pair_count.data_ptr())
+        if match_index is not None:
+            r.match_index = match_index.data_ptr()
+        if report is not None:  # (new_indices, new_count, broken_indices, broken_count, flag, offset, block_sum)
+            (r.new_indices, r.new_count, r.broken_indices, r.broken_count, r.flag, r.offset,
+             r.block_sum) = (x.data_ptr() for x in report)
+        return r
+
+    def _report(self, contacts, match_index, report=None):
+        dm = self.dm
+        _lib.check(dm.lib.nt_contacts_match_report(C.byref(dm.desc), C.byref(contacts._sorted),
+                                                   C.byref(self._report_desc(match_index, report)), dm.stream()),
+                   "nt_contacts_match_report")
+
+    def _save(self, state, contacts):
+        """The frame as the next frame's history: midpoints / normals / live flags (+ body-frame records), positions, count."""
+        dm, t = self.dm, self.model.env
+        if t.np * t.cpp > 0:
+            _lib.check(dm.lib.nt_contacts_save_history(C.byref(dm.desc), C.byref(state._desc()), C.byref(contacts._desc()),
+                                                       C.byref(self._h), dm.stream()), "nt_contacts_save_history")
+        if self._rows is not None:
+            self._rows.save_history(state, contacts._flat)
+        _lib.check(dm.lib.nt_contacts_order_save(C.byref(dm.desc), C.byref(contacts._sorted), C.byref(self._report_desc()), dm.stream()),
+                   "nt_contacts_order_save")
+
     def match(self, state, contacts):
         """-> int32 tensor over the CURRENT frame's flat contacts (export order): previous flat index, -1 or -2.  With
         CollisionPipeline(deterministic=True) both orders are the reference's key-sorted order."""
         torch = _torch()
+        if contacts.sort_by_key:
+            self._match_kernels(state, contacts)
+            e = contacts._exported()
+            out = torch.full((max(contacts.rigid_contact_max, 1),), -1, dtype=torch.int32, device=self.dm.device)
+            self._report(contacts, out)
+            self._reset_buf.zero_()
+            return out[: int(e["count"].item())]
         dm, t = self.dm, self.model.env
         d_s, d_c = state._desc(), contacts._desc()
         mask_ptr = self._reset_mask.data_ptr() if self._reset_mask is not None else None
@@ -375,6 +575,10 @@ class ContactMatcher:
 
     def save_sorted_state(self, state, contacts):
         """Persist this frame's contacts as the next frame's history (call after match, with the state they were made on)."""
+        if contacts.sort_by_key:
+            contacts._exported()  # (the positions of this frame's slots / rows)
+            self._save(state, contacts)
+            return
         dm, t = self.dm, self.model.env
         d_s, d_c = state._desc(), contacts._desc()
         if t.np * t.cpp > 0:
@@ -498,7 +702,6 @@ class CollisionPipeline:
         self._matcher = (ContactMatcher(model, contact_matching_pos_threshold, contact_matching_normal_dot_threshold,
                                         sticky=contact_matching == "sticky", sdf_leg=self._sdf_leg)
                          if contact_matching != "disabled" else None)
-        self._prev_count = 0
 
     @property
     def rigid_contact_max(self):
@@ -512,11 +715,15 @@ class CollisionPipeline:
             torch = _torch()
             dev, n = self.dm.device, max(self._rigid_contact_max, 1)
             c.rigid_contact_match_index = torch.full((n,), -1, dtype=torch.int32, device=dev)
+            c._report_buffers = None
             if self.contact_report:
                 c.rigid_contact_new_indices = torch.zeros(n, dtype=torch.int32, device=dev)
                 c.rigid_contact_new_count = torch.zeros(1, dtype=torch.int32, device=dev)
                 c.rigid_contact_broken_indices = torch.zeros(n, dtype=torch.int32, device=dev)
                 c.rigid_contact_broken_count = torch.zeros(1, dtype=torch.int32, device=dev)
+                c._report_buffers = (c.rigid_contact_new_indices, c.rigid_contact_new_count, c.rigid_contact_broken_indices,
+                                     c.rigid_contact_broken_count, torch.zeros(n, dtype=torch.int32, device=dev),  # scan flags, offsets
+                                     torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n // 1024 + 2, dtype=torch.int32, device=dev))
         return c
 
     def reset_contact_matching(self, world_mask=None) -> None:
@@ -524,36 +731,23 @@ class CollisionPipeline:
         if self._matcher is None:
             raise ValueError('reset_contact_matching requires contact_matching != "disabled"')
         self._matcher.reset(world_mask)
-        if world_mask is None:
-            self._prev_count = 0
 
     def _match(self, state, contacts):
-        """contacts.rigid_contact_match_index (+ the new / broken report) for this frame, then save the frame as history."""
-        torch = _torch()
+        """contacts.rigid_contact_match_index (+ the new / broken report) for this frame, then save the frame as history -- device
+        work only (no host read, no allocation): a frame with this collide() records into a hipGraph."""
         if getattr(contacts, "rigid_contact_match_index", None) is None:
             raise ValueError("CollisionPipeline has contact_matching enabled but the Contacts buffer was created without it. "
                              "Use pipeline.contacts() to create a compatible buffer.")
-        m = self._matcher.match(state, contacts)
-        n = int(m.numel()) if int(contacts.rigid_contact_count[0].item()) > 0 else 0
-        contacts.rigid_contact_match_index.fill_(-1)
-        contacts.rigid_contact_match_index[:n] = m[:n]
-        if self.contact_report:
-            new = torch.nonzero(m[:n] < 0).flatten().to(torch.int32)
-            contacts.rigid_contact_new_indices[: new.numel()] = new
-            contacts.rigid_contact_new_count[0] = new.numel()
-            # broken: rows of the previous frame that no contact of this frame matched (worlds reset since are skipped by
-            # the matcher: their history is gone, so they report neither matches nor broken rows)
-            hit = torch.zeros(max(self._prev_count, 1), dtype=torch.bool, device=m.device)
-            ok = m[:n][m[:n] >= 0].to(torch.int64)
-            hit[ok] = True
-            live_prev = self._matcher.previous_rows_alive(self._prev_count)
-            broken = torch.nonzero(~hit[: self._prev_count] & live_prev).flatten().to(torch.int32)
-            contacts.rigid_contact_broken_indices[: broken.numel()] = broken
-            contacts.rigid_contact_broken_count[0] = broken.numel()
+        mt = self._matcher
+        mt._match_kernels(state, contacts)
         if self.contact_matching == "sticky":
-            self._matcher.replay_matched(state, contacts)
-        self._matcher.save_sorted_state(state, contacts)
-        self._prev_count = n
+            mt.replay_matched(state, contacts)
+        # the key-ordered views of the frame (after the replay: the geometry the solver sees) and the positions of its slots / rows
+        contacts._export_sorted()
+        # broken: rows of the previous frame that no contact of this frame matched (worlds reset since are skipped by the matcher:
+        # their history is gone, so they report neither matches nor broken rows)
+        mt._report(contacts, contacts.rigid_contact_match_index, contacts._report_buffers)
+        mt._save(state, contacts)
 
     def collide(self, state, contacts: Contacts, *, soft_contact_margin=None, dt=None):
         if contacts.model is not self.model:

@@ -12,6 +12,11 @@
 #include <stdint.h>
 
 #include "../../include/newton_hip.h"
+#ifndef NT_EMULATED_GRID
+#include "../../include/newton_hip_contacts.h"
+#else  // (the CPU emulator compiles a copy of this file from tests/emu/_build)
+#include "../../../include/newton_hip_contacts.h"
+#endif
 #include "nt_math.hpp"
 
 using namespace nt;
@@ -195,6 +200,431 @@ nt_status nt_contacts_save_history(const nt_model* m, const nt_state* s, const n
     MatchArgs a = {*m, *s, *c, *h, 0.0f, 0.0f, nullptr, nullptr};
     const size_t n = (size_t)m->np * m->cpp * m->env_stride;
     hipLaunchKernelGGL(contacts_save_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? NT_OK : NT_ERR_LAUNCH;
+}
+
+}  // extern "C"
+
+// ---- key-ordered export and matching report (include/newton_hip_contacts.h) -----------------------------------------------------
+// The order is a counting sort over buckets whose key rank is fixed at pipeline construction: per export the live contacts of
+// every bucket are counted (tile buckets: one lane per (pair, env) over its <= 5 slots; row buckets: one wave per world walking
+// its rows in order, the per-bucket fill in LDS), the counts are scanned in rank order (three-kernel multi-block scan, integer
+// sums: the same result whatever the schedule), and every live slot / row is written to bucket_start[rank] + its position inside
+// the bucket.  Streaming, one lane per slot / row / output entry, no atomics on the data path.
+namespace {
+
+// components of nt_contacts.data (nt_layout.hpp CD_*)
+constexpr int CD_POINT0 = 0, CD_POINT1 = 3, CD_OFFSET0 = 6, CD_OFFSET1 = 9, CD_NORMAL = 12, CD_MARGIN0 = 15, CD_MARGIN1 = 16;
+constexpr int SCAN_THREADS = 256, SCAN_ITEMS = 4, SCAN_CHUNK = SCAN_THREADS * SCAN_ITEMS;
+
+unsigned grid_for(size_t n, unsigned threads) {
+    size_t b = (n + threads - 1) / threads;
+#ifdef NT_EMULATED_GRID
+    if (b > NT_EMULATED_GRID) b = NT_EMULATED_GRID;
+#else
+    if (b > 16384) b = 16384;  // (grid-stride loops cover the rest)
+#endif
+    return b < 1 ? 1u : (unsigned)b;
+}
+__host__ __device__ inline int scan_chunks(int n) { return (n + SCAN_CHUNK - 1) / SCAN_CHUNK; }
+
+// exclusive scan of in[0, n) into out, chunk totals through block_sum ([chunks + 1]); *total (nullable) = the sum
+__global__ void __launch_bounds__(SCAN_THREADS) scan_partial_kernel(const int32_t* in, int n, int32_t* block_sum) {
+    __shared__ int32_t part[SCAN_THREADS];
+    const int chunks = scan_chunks(n), t = threadIdx.x;
+    for (int ch = blockIdx.x; ch < chunks; ch += gridDim.x) {
+        int s = 0;
+        for (int k = 0; k < SCAN_ITEMS; ++k) {
+            const int i = ch * SCAN_CHUNK + t * SCAN_ITEMS + k;
+            if (i < n) s += in[i];
+        }
+        part[t] = s;
+        __syncthreads();
+        for (int w = SCAN_THREADS / 2; w > 0; w >>= 1) {
+            if (t < w) part[t] += part[t + w];
+            __syncthreads();
+        }
+        if (t == 0) block_sum[ch] = part[0];
+        __syncthreads();
+    }
+}
+__global__ void __launch_bounds__(SCAN_THREADS) scan_top_kernel(int32_t* block_sum, int chunks, int32_t* total) {
+    __shared__ int32_t part[SCAN_THREADS];
+    const int t = threadIdx.x, per = (chunks + SCAN_THREADS - 1) / SCAN_THREADS;
+    const int beg = t * per, end = beg + per < chunks ? beg + per : chunks;
+    int s = 0;
+    for (int i = beg; i < end; ++i) s += block_sum[i];
+    part[t] = s;
+    __syncthreads();
+    if (t == 0) {
+        int acc = 0;
+        for (int i = 0; i < SCAN_THREADS; ++i) { const int v = part[i]; part[i] = acc; acc += v; }
+        block_sum[chunks] = acc;
+        if (total) total[0] = acc;
+    }
+    __syncthreads();
+    int acc = part[t];
+    for (int i = beg; i < end; ++i) { const int v = block_sum[i]; block_sum[i] = acc; acc += v; }
+}
+__global__ void __launch_bounds__(SCAN_THREADS) scan_apply_kernel(const int32_t* in, int n, const int32_t* block_sum, int32_t* out) {
+    __shared__ int32_t part[SCAN_THREADS];
+    const int chunks = scan_chunks(n), t = threadIdx.x;
+    for (int ch = blockIdx.x; ch < chunks; ch += gridDim.x) {
+        int v[SCAN_ITEMS], s = 0;
+        for (int k = 0; k < SCAN_ITEMS; ++k) {
+            const int i = ch * SCAN_CHUNK + t * SCAN_ITEMS + k;
+            v[k] = i < n ? in[i] : 0;
+            s += v[k];
+        }
+        part[t] = s;
+        __syncthreads();
+        if (t == 0) {
+            int acc = block_sum[ch];
+            for (int i = 0; i < SCAN_THREADS; ++i) { const int x = part[i]; part[i] = acc; acc += x; }
+        }
+        __syncthreads();
+        int acc = part[t];
+        for (int k = 0; k < SCAN_ITEMS; ++k) {
+            const int i = ch * SCAN_CHUNK + t * SCAN_ITEMS + k;
+            if (i < n) out[i] = acc;
+            acc += v[k];
+        }
+        __syncthreads();
+    }
+}
+void launch_scan(const int32_t* in, int n, int32_t* block_sum, int32_t* out, int32_t* total, hipStream_t st) {
+    const int chunks = scan_chunks(n);
+    const unsigned g = grid_for((size_t)chunks, 1);
+    hipLaunchKernelGGL(scan_partial_kernel, dim3(g), dim3(SCAN_THREADS), 0, st, in, n, block_sum);
+    hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, block_sum, chunks, total);
+    hipLaunchKernelGGL(scan_apply_kernel, dim3(g), dim3(SCAN_THREADS), 0, st, in, n, block_sum, out);
+}
+
+// live slot contacts of every tile bucket (pair p, env e, orientation o)
+__global__ void __launch_bounds__(256) order_tile_count_kernel(nt_model m, nt_contacts c, nt_contact_order o) {
+    const int E = m.env_count, ES = m.env_stride, cpp = m.cpp;
+    const size_t n = (size_t)m.np * E;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int p = (int)(i / E), env = (int)(i % E);
+        const int want0 = o.tile_shape0[i];
+        int cnt[2] = {0, 0};
+        for (int k = 0; k < cpp; ++k) {
+            const int s0 = c.shape0[(size_t)(p * cpp + k) * ES + env];
+            if (s0 < 0) continue;
+            cnt[s0 == want0 ? 0 : 1] += 1;
+        }
+        o.bucket_fill[o.tile_rank[2 * i]] = cnt[0];
+        o.bucket_fill[o.tile_rank[2 * i + 1]] = cnt[1];
+    }
+}
+
+// the rows of one world, 64 at a time in row order: bucket by binary search of the row's key in the world's table, position inside
+// the bucket = the bucket's fill so far + the lanes of this round before it with the same bucket
+constexpr int ROW_WAVE = 64;
+__global__ void __launch_bounds__(ROW_WAVE) order_row_bucket_kernel(nt_model m, nt_flat_rows f, int row_capacity, nt_contact_order o) {
+    extern __shared__ __align__(16) float lds[];
+    const int K = o.row_keys, E = m.env_count, t = threadIdx.x;
+    int32_t* fill = (int32_t*)lds;  // [K]
+    int32_t* lane_bucket = fill + K;  // [ROW_WAVE]
+    const int nf = f.row_start[E] < row_capacity ? f.row_start[E] : row_capacity;
+    for (int w = blockIdx.x; w < E; w += gridDim.x) {
+        for (int j = t; j < K; j += ROW_WAVE) fill[j] = 0;
+        __syncthreads();
+        const int r0 = f.row_start[w] < nf ? f.row_start[w] : nf, r1 = f.row_start[w + 1] < nf ? f.row_start[w + 1] : nf;
+        const int64_t* keys = o.row_key + (size_t)w * K;
+        for (int base = r0; base < r1; base += ROW_WAVE) {  // (uniform trip count over the block)
+            const int i = base + t;
+            int b = -1;
+            if (i < r1) {
+                const int s0 = f.shape0[i], s1 = f.shape1[i];
+                if (s0 != s1) {
+                    const int64_t key = (int64_t)s0 * ((int64_t)1 << 32) + (int64_t)s1;
+                    int lo = 0, hi = K;  // lower bound
+                    while (lo < hi) {
+                        const int mid = (lo + hi) >> 1;
+                        if (keys[mid] < key) lo = mid + 1;
+                        else hi = mid;
+                    }
+                    if (lo < K && keys[lo] == key) b = lo;
+                    else atomicAdd(o.row_unmatched, 1);
+                }
+            }
+            lane_bucket[t] = b;
+            __syncthreads();
+            int sub = 0;
+            bool last = b >= 0;
+            if (b >= 0) {
+                int before = 0;
+                for (int u = 0; u < ROW_WAVE; ++u) {
+                    if (lane_bucket[u] != b) continue;
+                    if (u < t) before += 1;
+                    else if (u > t) last = false;
+                }
+                sub = fill[b] + before;
+            }
+            if (i < r1) {
+                o.row_bucket[i] = b >= 0 ? o.row_rank[(size_t)w * K + b] : -1;
+                o.row_sub[i] = sub;
+            }
+            __syncthreads();
+            if (last) fill[b] = sub + 1;
+            __syncthreads();
+        }
+        for (int j = t; j < K; j += ROW_WAVE) o.bucket_fill[o.row_rank[(size_t)w * K + j]] = fill[j];
+        __syncthreads();
+    }
+}
+
+__device__ inline void st3v(float* p, size_t i, float x, float y, float z) { p[3 * i] = x; p[3 * i + 1] = y; p[3 * i + 2] = z; }
+
+__global__ void __launch_bounds__(256) order_slot_scatter_kernel(nt_model m, nt_contacts c, nt_contact_order o, nt_sorted_contacts s) {
+    const int E = m.env_count, ES = m.env_stride, cpp = m.cpp, ncs = m.np * cpp;
+    const size_t n = (size_t)ncs * ES;
+    for (size_t gi = (size_t)blockIdx.x * blockDim.x + threadIdx.x; gi < n; gi += (size_t)gridDim.x * blockDim.x) {
+        const int slot = (int)(gi / ES), env = (int)(gi % ES);
+        const int s0 = env < E ? c.shape0[gi] : -1;
+        if (s0 < 0) { s.slot_flat[gi] = -1; continue; }
+        const int p = slot / cpp, k = slot - p * cpp;
+        const size_t pe = (size_t)p * E + env;
+        const int want0 = o.tile_shape0[pe], orient = s0 == want0 ? 0 : 1;
+        int sub = 0;
+        for (int k2 = 0; k2 < k; ++k2) {
+            const int x = c.shape0[(size_t)(p * cpp + k2) * ES + env];
+            if (x >= 0 && (x == want0 ? 0 : 1) == orient) sub += 1;
+        }
+        const int idx = o.bucket_start[o.tile_rank[2 * pe + orient]] + sub;
+        s.slot_flat[gi] = idx;
+        if (idx >= s.cap) continue;
+        const float* D = c.data;
+        auto ld = [&](int comp) { return D[((size_t)comp * ncs + slot) * ES + env]; };
+        s.shape0[idx] = s0;
+        s.shape1[idx] = c.shape1[gi];
+        st3v(s.point0, idx, ld(CD_POINT0), ld(CD_POINT0 + 1), ld(CD_POINT0 + 2));
+        st3v(s.point1, idx, ld(CD_POINT1), ld(CD_POINT1 + 1), ld(CD_POINT1 + 2));
+        st3v(s.offset0, idx, ld(CD_OFFSET0), ld(CD_OFFSET0 + 1), ld(CD_OFFSET0 + 2));
+        st3v(s.offset1, idx, ld(CD_OFFSET1), ld(CD_OFFSET1 + 1), ld(CD_OFFSET1 + 2));
+        st3v(s.normal, idx, ld(CD_NORMAL), ld(CD_NORMAL + 1), ld(CD_NORMAL + 2));
+        s.margin0[idx] = ld(CD_MARGIN0);
+        s.margin1[idx] = ld(CD_MARGIN1);
+        if (s.stiffness) {
+            const float* P = c.prop;
+            s.stiffness[idx] = P ? P[((size_t)0 * ncs + slot) * ES + env] : 0.0f;
+            s.damping[idx] = P ? P[((size_t)1 * ncs + slot) * ES + env] : 0.0f;
+            s.friction[idx] = P ? P[((size_t)2 * ncs + slot) * ES + env] : 0.0f;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) order_row_scatter_kernel(nt_model m, nt_flat_rows f, nt_contact_order o, nt_sorted_contacts s) {
+    const int E = m.env_count;
+    const int nf = f.row_start[E] < s.row_capacity ? f.row_start[E] : s.row_capacity;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < s.row_capacity; i += gridDim.x * blockDim.x) {
+        const int b = i < nf ? o.row_bucket[i] : -1;
+        if (b < 0) { s.row_flat[i] = -1; continue; }
+        const int idx = o.bucket_start[b] + o.row_sub[i];
+        s.row_flat[i] = idx;
+        if (idx >= s.cap) continue;
+        s.shape0[idx] = f.shape0[i];
+        s.shape1[idx] = f.shape1[i];
+        for (int k = 0; k < 3; ++k) {
+            s.point0[3 * (size_t)idx + k] = f.point0[3 * (size_t)i + k];
+            s.point1[3 * (size_t)idx + k] = f.point1[3 * (size_t)i + k];
+            s.offset0[3 * (size_t)idx + k] = f.offset0[3 * (size_t)i + k];
+            s.offset1[3 * (size_t)idx + k] = f.offset1[3 * (size_t)i + k];
+            s.normal[3 * (size_t)idx + k] = f.normal[3 * (size_t)i + k];
+        }
+        s.margin0[idx] = f.margin0[i];
+        s.margin1[idx] = f.margin1[i];
+        if (s.stiffness) {
+            s.stiffness[idx] = f.stiffness ? f.stiffness[i] : 0.0f;
+            s.damping[idx] = f.stiffness ? f.damping[i] : 0.0f;
+            s.friction[idx] = f.stiffness ? f.friction_scale[i] : 0.0f;
+        }
+    }
+}
+
+// entries at or beyond the count: what a freshly filled export holds (-1 ids, 0 floats)
+__global__ void __launch_bounds__(256) order_tail_kernel(nt_sorted_contacts s) {
+    const int n = s.count[0];
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < s.cap; i += gridDim.x * blockDim.x) {
+        if (i < n) continue;
+        s.shape0[i] = -1;
+        s.shape1[i] = -1;
+        st3v(s.point0, i, 0.0f, 0.0f, 0.0f);
+        st3v(s.point1, i, 0.0f, 0.0f, 0.0f);
+        st3v(s.offset0, i, 0.0f, 0.0f, 0.0f);
+        st3v(s.offset1, i, 0.0f, 0.0f, 0.0f);
+        st3v(s.normal, i, 0.0f, 0.0f, 0.0f);
+        s.margin0[i] = 0.0f;
+        s.margin1[i] = 0.0f;
+        if (s.stiffness) { s.stiffness[i] = 0.0f; s.damping[i] = 0.0f; s.friction[i] = 0.0f; }
+    }
+}
+
+// match_index: the previous slot / row each contact matched, as its position in the previous frame's arrays
+__global__ void __launch_bounds__(256) report_map_slots_kernel(nt_model m, nt_sorted_contacts s, nt_contact_report r) {
+    const int E = m.env_count, ES = m.env_stride;
+    const size_t n = (size_t)m.np * m.cpp * ES;
+    for (size_t gi = (size_t)blockIdx.x * blockDim.x + threadIdx.x; gi < n; gi += (size_t)gridDim.x * blockDim.x) {
+        const int env = (int)(gi % ES), idx = s.slot_flat[gi];
+        if (env >= E || idx < 0 || idx >= s.cap) continue;
+        int v = r.slot_match[gi];
+        if (v >= 0) v = r.prev_slot_flat[(size_t)v * ES + env];
+        r.match_index[idx] = v;
+    }
+}
+__global__ void __launch_bounds__(256) report_map_rows_kernel(nt_sorted_contacts s, nt_contact_report r) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < s.row_capacity; i += gridDim.x * blockDim.x) {
+        const int idx = s.row_flat[i];
+        if (idx < 0 || idx >= s.cap) continue;
+        int v = r.row_match[i];
+        if (v >= 0) v = r.prev_row_flat[v];
+        r.match_index[idx] = v;
+    }
+}
+// tail of match_index (-1) + the flags of the new list
+__global__ void __launch_bounds__(256) report_new_flags_kernel(nt_sorted_contacts s, nt_contact_report r, int with_report) {
+    const int n = s.count[0];
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < s.cap; i += gridDim.x * blockDim.x) {
+        if (i >= n) r.match_index[i] = -1;
+        if (with_report) r.flag[i] = i < n && r.match_index[i] < 0 ? 1 : 0;
+    }
+}
+__global__ void __launch_bounds__(256) report_compact_kernel(int cap, const int32_t* flag, const int32_t* offset, int32_t* out) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < cap; i += gridDim.x * blockDim.x)
+        if (flag[i]) out[offset[i]] = i;
+}
+// broken list, step 1: clear the flags
+__global__ void __launch_bounds__(256) report_clear_kernel(int cap, int32_t* flag) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < cap; i += gridDim.x * blockDim.x) flag[i] = 0;
+}
+// step 2: the previous frame's contacts whose history is still alive (slots: prev_live, cleared by a world reset)
+__global__ void __launch_bounds__(256) report_alive_slots_kernel(nt_model m, nt_sorted_contacts s, nt_contact_report r) {
+    const int E = m.env_count, ES = m.env_stride;
+    const size_t n = (size_t)m.np * m.cpp * ES;
+    const int pc = r.prev_count[0];
+    for (size_t gi = (size_t)blockIdx.x * blockDim.x + threadIdx.x; gi < n; gi += (size_t)gridDim.x * blockDim.x) {
+        const int env = (int)(gi % ES), idx = r.prev_slot_flat[gi];
+        if (env < E && idx >= 0 && idx < pc && idx < s.cap && r.prev_slot_live[gi]) r.flag[idx] = 1;
+    }
+}
+// (rows: prev_live, and the row's world still has its previous pairs)
+__global__ void __launch_bounds__(256) report_alive_rows_kernel(nt_model m, nt_sorted_contacts s, nt_contact_report r) {
+    const int E = m.env_count, pc = r.prev_count[0];
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < s.row_capacity; i += gridDim.x * blockDim.x) {
+        const int idx = r.prev_row_flat[i];
+        if (idx < 0 || idx >= pc || idx >= s.cap || !r.prev_row_live[i]) continue;
+        int lo = 0, hi = E;  // world = number of w with prev_row_start[w + 1] <= i
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (r.prev_row_start[mid + 1] <= i) lo = mid + 1;
+            else hi = mid;
+        }
+        if (lo < E && r.prev_pair_count[lo] > 0) r.flag[idx] = 1;
+    }
+}
+// step 3: the ones this frame matched are not broken
+__global__ void __launch_bounds__(256) report_hit_kernel(nt_sorted_contacts s, nt_contact_report r) {
+    const int n = s.count[0] < s.cap ? s.count[0] : s.cap, pc = r.prev_count[0];
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const int v = r.match_index[i];
+        if (v >= 0 && v < pc && v < s.cap) r.flag[v] = 0;
+    }
+}
+
+__global__ void __launch_bounds__(256) order_save_kernel(nt_model m, nt_sorted_contacts s, nt_contact_report r) {
+    const size_t ns = (size_t)m.np * m.cpp * m.env_stride;
+    size_t n = ns > (size_t)s.row_capacity ? ns : (size_t)s.row_capacity;
+    if (n < (size_t)m.env_count) n = (size_t)m.env_count;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        if (i < ns) r.prev_slot_flat[i] = s.slot_flat[i];
+        if (i < (size_t)s.row_capacity && r.prev_row_flat) r.prev_row_flat[i] = s.row_flat[i];
+        if (i == 0) r.prev_count[0] = s.count[0];
+        if (r.reset_world_mask && i < (size_t)m.env_count) r.reset_world_mask[i] = 0;
+    }
+}
+
+bool sorted_ok(const nt_model* m, const nt_sorted_contacts* s) {
+    return m && s && m->env_count > 0 && s->cap > 0 && s->row_capacity >= 0 && s->count && s->shape0 && s->shape1 && s->point0 &&
+           s->point1 && s->offset0 && s->offset1 && s->normal && s->margin0 && s->margin1 && (m->np == 0 || s->slot_flat) &&
+           (s->row_capacity == 0 || s->row_flat) && (!s->stiffness || (s->damping && s->friction));
+}
+
+}  // namespace
+
+extern "C" {
+
+nt_status nt_contacts_export_sorted(const nt_model* m, const nt_contacts* c, const nt_contact_order* o, nt_sorted_contacts* out,
+                                    void* stream) {
+    if (!c || !o || !sorted_ok(m, out) || o->bucket_count < 0 || !o->bucket_fill || !o->bucket_start || !o->block_sum)
+        return NT_ERR_INVALID_ARG;
+    const int E = m->env_count;
+    const bool slots = m->np > 0, rows = out->row_capacity > 0;
+    if (slots && (!c->shape0 || !c->shape1 || !c->data || !o->tile_shape0 || !o->tile_rank)) return NT_ERR_INVALID_ARG;
+    if (rows && (!c->flat.row_start || !c->flat.shape0 || o->row_keys <= 0 || !o->row_key || !o->row_rank || !o->row_bucket ||
+                 !o->row_sub || !o->row_unmatched))
+        return NT_ERR_INVALID_ARG;
+    if (o->bucket_count != 2 * E * m->np + (rows ? E * o->row_keys : 0)) return NT_ERR_INVALID_ARG;
+    const size_t row_lds = rows ? sizeof(int32_t) * ((size_t)o->row_keys + ROW_WAVE) : 0;
+    if (row_lds > 64 * 1024) return NT_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    if (slots)
+        hipLaunchKernelGGL(order_tile_count_kernel, dim3(grid_for((size_t)m->np * E, 256)), dim3(256), 0, st, *m, *c, *o);
+    if (rows)
+        hipLaunchKernelGGL(order_row_bucket_kernel, dim3(grid_for((size_t)E, 1)), dim3(ROW_WAVE), row_lds, st, *m, c->flat,
+                           out->row_capacity, *o);
+    if (o->bucket_count > 0) {
+        launch_scan(o->bucket_fill, o->bucket_count, o->block_sum, o->bucket_start, out->count, st);
+    } else if (hipMemsetAsync(out->count, 0, sizeof(int32_t), st) != hipSuccess) {
+        return NT_ERR_LAUNCH;
+    }
+    if (slots)
+        hipLaunchKernelGGL(order_slot_scatter_kernel, dim3(grid_for((size_t)m->np * m->cpp * m->env_stride, 256)), dim3(256), 0, st,
+                           *m, *c, *o, *out);
+    if (rows)
+        hipLaunchKernelGGL(order_row_scatter_kernel, dim3(grid_for((size_t)out->row_capacity, 256)), dim3(256), 0, st, *m, c->flat, *o,
+                           *out);
+    hipLaunchKernelGGL(order_tail_kernel, dim3(grid_for((size_t)out->cap, 256)), dim3(256), 0, st, *out);
+    return hipGetLastError() == hipSuccess ? NT_OK : NT_ERR_LAUNCH;
+}
+
+nt_status nt_contacts_match_report(const nt_model* m, const nt_sorted_contacts* s, const nt_contact_report* r, void* stream) {
+    if (!sorted_ok(m, s) || !r || !r->prev_count || !r->match_index) return NT_ERR_INVALID_ARG;
+    const bool slots = m->np > 0, rows = s->row_capacity > 0, report = r->new_indices != nullptr;
+    if (slots && (!r->prev_slot_flat || !r->slot_match || !r->prev_slot_live)) return NT_ERR_INVALID_ARG;
+    if (rows && (!r->prev_row_flat || !r->row_match || !r->prev_row_live || !r->prev_row_start || !r->prev_pair_count))
+        return NT_ERR_INVALID_ARG;
+    if (report && (!r->new_count || !r->broken_indices || !r->broken_count || !r->flag || !r->offset || !r->block_sum))
+        return NT_ERR_INVALID_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t nslot = (size_t)m->np * m->cpp * m->env_stride;
+    const unsigned gc = grid_for((size_t)s->cap, 256);
+    if (slots) hipLaunchKernelGGL(report_map_slots_kernel, dim3(grid_for(nslot, 256)), dim3(256), 0, st, *m, *s, *r);
+    if (rows) hipLaunchKernelGGL(report_map_rows_kernel, dim3(grid_for((size_t)s->row_capacity, 256)), dim3(256), 0, st, *s, *r);
+    hipLaunchKernelGGL(report_new_flags_kernel, dim3(gc), dim3(256), 0, st, *s, *r, report ? 1 : 0);
+    if (report) {
+        launch_scan(r->flag, s->cap, r->block_sum, r->offset, r->new_count, st);
+        hipLaunchKernelGGL(report_compact_kernel, dim3(gc), dim3(256), 0, st, s->cap, (const int32_t*)r->flag, (const int32_t*)r->offset,
+                           r->new_indices);
+        hipLaunchKernelGGL(report_clear_kernel, dim3(gc), dim3(256), 0, st, s->cap, r->flag);
+        if (slots) hipLaunchKernelGGL(report_alive_slots_kernel, dim3(grid_for(nslot, 256)), dim3(256), 0, st, *m, *s, *r);
+        if (rows)
+            hipLaunchKernelGGL(report_alive_rows_kernel, dim3(grid_for((size_t)s->row_capacity, 256)), dim3(256), 0, st, *m, *s, *r);
+        hipLaunchKernelGGL(report_hit_kernel, dim3(gc), dim3(256), 0, st, *s, *r);
+        launch_scan(r->flag, s->cap, r->block_sum, r->offset, r->broken_count, st);
+        hipLaunchKernelGGL(report_compact_kernel, dim3(gc), dim3(256), 0, st, s->cap, (const int32_t*)r->flag, (const int32_t*)r->offset,
+                           r->broken_indices);
+    }
+    return hipGetLastError() == hipSuccess ? NT_OK : NT_ERR_LAUNCH;
+}
+
+nt_status nt_contacts_order_save(const nt_model* m, const nt_sorted_contacts* s, const nt_contact_report* r, void* stream) {
+    if (!sorted_ok(m, s) || !r || !r->prev_count || (m->np > 0 && !r->prev_slot_flat) || (s->row_capacity > 0 && !r->prev_row_flat))
+        return NT_ERR_INVALID_ARG;
+    const size_t nslot = (size_t)m->np * m->cpp * m->env_stride;
+    size_t n = nslot > (size_t)s->row_capacity ? nslot : (size_t)s->row_capacity;
+    if (n < (size_t)m->env_count) n = (size_t)m->env_count;
+    hipLaunchKernelGGL(order_save_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, *m, *s, *r);
     return hipGetLastError() == hipSuccess ? NT_OK : NT_ERR_LAUNCH;
 }
 
