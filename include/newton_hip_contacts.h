@@ -101,6 +101,41 @@ nt_status nt_contacts_match_report(const nt_model* m, const nt_sorted_contacts* 
 /* the frame as the next frame's previous one: positions, count; clears reset_world_mask */
 nt_status nt_contacts_order_save(const nt_model* m, const nt_sorted_contacts* sorted, const nt_contact_report* r, void* stream);
 
+/* ---- heterogeneous models: one key-ordered export over several world groups ----------------------------------------------------
+ * A model whose worlds differ in topology runs as world groups, each a homogeneous model of its own (group-local shape ids).  The
+ * export over all of them is the same counting sort: every group's buckets get GLOBAL ranks (one stable argsort of all groups'
+ * bucket keys, in global shape ids, enumerated in the raw heterogeneous order: every group's analytic tile buckets in group order,
+ * then per group its convex tile buckets and its row buckets), the per-group count passes fill disjoint entries of one
+ * bucket_fill, one scan runs over all of them and the per-group scatters write one set of arrays, translating shape ids. */
+typedef struct {
+    const nt_model* m;              /* the group's model */
+    const nt_contacts* c;           /* its contacts (group-local shape ids) */
+    const nt_contact_order* o;      /* its table: bucket_count = the group's own B, ranks GLOBAL (0 <= rank < the global bucket
+                                     * count), row scratch of its own; its bucket_fill / bucket_start / block_sum are not used */
+    const int32_t* shape_id;        /* [group shape count] global id of every shape of the group (increasing) */
+    int32_t row_capacity;           /* capacity of c->flat (0: no rows) */
+    int32_t* slot_flat;             /* [np*cpp][ES] out: global position of every live slot, -1 otherwise */
+    int32_t* row_flat;              /* [row_capacity] out: global position of every live row, -1 otherwise */
+    const nt_contact_report* r;     /* the group's matching state, or NULL without matching: prev_slot_flat / prev_row_flat (GLOBAL
+                                     * positions), slot_match, row_match, prev_slot_live, prev_row_live, prev_row_start,
+                                     * prev_pair_count, reset_world_mask; its other fields are not used */
+} nt_contact_group;
+
+/* `o`: the global scan (bucket_count = sum of the groups' B, bucket_fill / bucket_start [bucket_count], block_sum
+ * [bucket_count / 1024 + 2]; its other fields are not used).  `out`: the global arrays (cap, count, shape0 ...), its row_capacity /
+ * slot_flat / row_flat are not used.  Writes every entry of `out`, the groups' slot_flat / row_flat, shape ids global. */
+nt_status nt_contacts_export_sorted_groups(int32_t group_count, const nt_contact_group* groups, const nt_contact_order* o,
+                                           nt_sorted_contacts* out, void* stream);
+/* nt_contacts_match_report over the groups: match_index in global positions, the new / broken lists over the global arrays.  `r`:
+ * prev_count, match_index, new_indices ... block_sum of the global arrays (its per-group fields are not used); every group
+ * carries its own `r` */
+nt_status nt_contacts_match_report_groups(int32_t group_count, const nt_contact_group* groups, const nt_sorted_contacts* sorted,
+                                          const nt_contact_report* r, void* stream);
+/* nt_contacts_order_save over the groups: every group's positions, the global count into r->prev_count, clears every group's
+ * reset_world_mask */
+nt_status nt_contacts_order_save_groups(int32_t group_count, const nt_contact_group* groups, const nt_sorted_contacts* sorted,
+                                        const nt_contact_report* r, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

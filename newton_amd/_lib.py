@@ -233,6 +233,12 @@ class nt_contact_report(C.Structure):
                 ("offset", C.c_void_p), ("block_sum", C.c_void_p)]
 
 
+class nt_contact_group(C.Structure):
+    """include/newton_hip_contacts.h: one world group of a heterogeneous model in the export / report / save over all groups."""
+    _fields_ = [("m", C.POINTER(nt_model)), ("c", C.POINTER(nt_contacts)), ("o", C.POINTER(nt_contact_order)), ("shape_id", C.c_void_p),
+                ("row_capacity", C.c_int32), ("slot_flat", C.c_void_p), ("row_flat", C.c_void_p), ("r", C.POINTER(nt_contact_report))]
+
+
 class nt_hydro_args(C.Structure):
     _fields_ = [("pairs", C.c_void_p), ("pair_count", C.c_int32), ("shape_transform", C.c_void_p), ("shape_data", C.c_void_p),
                 ("shape_gap", C.c_void_p), ("shape_kh", C.c_void_p), ("shape_sdf_index", C.c_void_p), ("sdf_table", C.c_void_p),
@@ -415,6 +421,12 @@ SYMBOLS = {
                                               C.POINTER(nt_sorted_contacts), _P]),
     "nt_contacts_match_report": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_sorted_contacts), C.POINTER(nt_contact_report), _P]),
     "nt_contacts_order_save": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_sorted_contacts), C.POINTER(nt_contact_report), _P]),
+    "nt_contacts_export_sorted_groups": (C.c_int32, [C.c_int32, C.POINTER(nt_contact_group), C.POINTER(nt_contact_order),
+                                                     C.POINTER(nt_sorted_contacts), _P]),
+    "nt_contacts_match_report_groups": (C.c_int32, [C.c_int32, C.POINTER(nt_contact_group), C.POINTER(nt_sorted_contacts),
+                                                    C.POINTER(nt_contact_report), _P]),
+    "nt_contacts_order_save_groups": (C.c_int32, [C.c_int32, C.POINTER(nt_contact_group), C.POINTER(nt_sorted_contacts),
+                                                  C.POINTER(nt_contact_report), _P]),
     "nt_hydro_collide": (C.c_int32, [C.POINTER(nt_hydro_args), _P]),
     "nt_hydro_pairs": (C.c_int32, [C.POINTER(nt_hydro_args), _P]),
     "nt_sdf_candidate_pairs": (C.c_int32, [C.POINTER(nt_sdf_scene), _P, _P, _P, _P, _P, _P]),

@@ -34,6 +34,17 @@ def _newton_ids(t, local, world):
     return np.where(local < t.ns, t.shape_local0 + world * t.ns + local, g)
 
 
+def _tile_shape_ids(t):
+    """[P, E] Newton ids (shape0, shape1) of orientation 0 of every (device pair, env): the tile writes its contacts type-sorted
+    (nt_match.hip midpoint)."""
+    E, P = t.env_count, t.np
+    w = np.arange(E)[None, :]
+    pa, pb = np.asarray(t.pair_a, np.int64)[:, None], np.asarray(t.pair_b, np.int64)[:, None]
+    ty = np.asarray(t.tile_shape_type, np.int64)
+    swap = ty[pa] > ty[pb] if P else np.zeros((0, 1), bool)
+    return _newton_ids(t, np.where(swap, pb, pa), w), _newton_ids(t, np.where(swap, pa, pb), w)
+
+
 def contact_order_tables(model):
     """Host tables of the key-ordered export (nt_contact_order, include/newton_hip_contacts.h), built once per model: the orientation-0
     shape0 of every (device pair, env), the row keys of every world (both orientations of every pair the SDF legs may route) and the
@@ -44,10 +55,7 @@ def contact_order_tables(model):
     t = model.env
     E, P, npa = t.env_count, t.np, t.np_analytic
     w = np.arange(E)[None, :]
-    pa, pb = np.asarray(t.pair_a, np.int64)[:, None], np.asarray(t.pair_b, np.int64)[:, None]
-    ty = np.asarray(t.tile_shape_type, np.int64)
-    swap = ty[pa] > ty[pb] if P else np.zeros((0, 1), bool)  # the tile writes its contacts type-sorted (nt_match.hip midpoint)
-    a, b = _newton_ids(t, np.where(swap, pb, pa), w), _newton_ids(t, np.where(swap, pa, pb), w)  # [P, E]
+    a, b = _tile_shape_ids(t)  # [P, E]
     tile_key = np.stack([(a << 32) + b, (b << 32) + a], axis=-1)  # [P, E, 2]
     ids = np.arange(P * E * 2).reshape(P, E, 2)
     keys, tile_ids = [], []
@@ -503,14 +511,19 @@ class ContactMatcher:
                                                    C.byref(self._report_desc(match_index, report)), dm.stream()),
                    "nt_contacts_match_report")
 
-    def _save(self, state, contacts):
-        """The frame as the next frame's history: midpoints / normals / live flags (+ body-frame records), positions, count."""
+    def _save_history(self, state, contacts):
+        """The frame's midpoints / normals / live flags (+ body-frame records) as the next frame's history."""
         dm, t = self.dm, self.model.env
         if t.np * t.cpp > 0:
             _lib.check(dm.lib.nt_contacts_save_history(C.byref(dm.desc), C.byref(state._desc()), C.byref(contacts._desc()),
                                                        C.byref(self._h), dm.stream()), "nt_contacts_save_history")
         if self._rows is not None:
             self._rows.save_history(state, contacts._flat)
+
+    def _save(self, state, contacts):
+        """The frame as the next frame's history: midpoints / normals / live flags (+ body-frame records), positions, count."""
+        dm = self.dm
+        self._save_history(state, contacts)
         _lib.check(dm.lib.nt_contacts_order_save(C.byref(dm.desc), C.byref(contacts._sorted), C.byref(self._report_desc()), dm.stream()),
                    "nt_contacts_order_save")
 
@@ -626,6 +639,35 @@ def estimate_rigid_contact_max(model) -> int:
     return max(_RIGID_CONTACT_MIN_CAPACITY, total)
 
 
+def add_matching_buffers(c, rigid_contact_max, report, dev):
+    """rigid_contact_match_index (+ the new / broken lists and the scratch of their scans) on a Contacts object."""
+    torch = _torch()
+    n = max(rigid_contact_max, 1)
+    c.rigid_contact_match_index = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    c._report_buffers = None
+    if report:
+        c.rigid_contact_new_indices = torch.zeros(n, dtype=torch.int32, device=dev)
+        c.rigid_contact_new_count = torch.zeros(1, dtype=torch.int32, device=dev)
+        c.rigid_contact_broken_indices = torch.zeros(n, dtype=torch.int32, device=dev)
+        c.rigid_contact_broken_count = torch.zeros(1, dtype=torch.int32, device=dev)
+        c._report_buffers = (c.rigid_contact_new_indices, c.rigid_contact_new_count, c.rigid_contact_broken_indices,
+                             c.rigid_contact_broken_count, torch.zeros(n, dtype=torch.int32, device=dev),  # scan flags, offsets
+                             torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n // 1024 + 2, dtype=torch.int32, device=dev))
+
+
+def check_matching_options(contact_matching, pos_threshold, normal_dot_threshold, contact_report):
+    """frame-to-frame matching (collide.py:1126-1129,1253-1268): "latest" fills contacts.rigid_contact_match_index every
+    collide(); "sticky" additionally replays last frame's contact geometry on matched rows that still touch"""
+    if contact_matching not in ("disabled", "latest", "sticky"):
+        raise ValueError(f"contact_matching must be one of 'disabled', 'latest', 'sticky', got {contact_matching!r}")
+    if pos_threshold < 0.0:
+        raise ValueError(f"contact_matching_pos_threshold must be non-negative, got {pos_threshold}")
+    if not -1.0 <= normal_dot_threshold <= 1.0:
+        raise ValueError(f"contact_matching_normal_dot_threshold must be in [-1, 1], got {normal_dot_threshold}")
+    if contact_report and contact_matching == "disabled":
+        raise ValueError('contact_report=True requires contact_matching != "disabled"')
+
+
 class CollisionPipeline:
     """newton.CollisionPipeline(model, *, broad_phase=..., rigid_contact_max=None, ...)  (collide.py:1104-1133).
 
@@ -655,16 +697,7 @@ class CollisionPipeline:
         if speculative_config is not None:
             raise NotImplementedError("speculative contacts (CollisionPipeline(speculative_config=...)) are not supported; "
                                       "pass None (the reference's default: collide(dt=...) is then ignored)")
-        # frame-to-frame matching (collide.py:1126-1129,1253-1268): "latest" fills contacts.rigid_contact_match_index every
-        # collide(); "sticky" additionally replays last frame's contact geometry on matched rows that still touch
-        if contact_matching not in ("disabled", "latest", "sticky"):
-            raise ValueError(f"contact_matching must be one of 'disabled', 'latest', 'sticky', got {contact_matching!r}")
-        if contact_matching_pos_threshold < 0.0:
-            raise ValueError(f"contact_matching_pos_threshold must be non-negative, got {contact_matching_pos_threshold}")
-        if not -1.0 <= contact_matching_normal_dot_threshold <= 1.0:
-            raise ValueError(f"contact_matching_normal_dot_threshold must be in [-1, 1], got {contact_matching_normal_dot_threshold}")
-        if contact_report and contact_matching == "disabled":
-            raise ValueError('contact_report=True requires contact_matching != "disabled"')
+        check_matching_options(contact_matching, contact_matching_pos_threshold, contact_matching_normal_dot_threshold, contact_report)
         if broad_phase not in self._BROAD_PHASES:
             raise ValueError(f"broad_phase must be one of 'nxn', 'sap', 'explicit', got {broad_phase!r}")
         self.model = model
@@ -712,18 +745,7 @@ class CollisionPipeline:
                      sdf_leg=self._sdf_leg)
         c._contact_matching_mode = self.contact_matching
         if self._matcher is not None:
-            torch = _torch()
-            dev, n = self.dm.device, max(self._rigid_contact_max, 1)
-            c.rigid_contact_match_index = torch.full((n,), -1, dtype=torch.int32, device=dev)
-            c._report_buffers = None
-            if self.contact_report:
-                c.rigid_contact_new_indices = torch.zeros(n, dtype=torch.int32, device=dev)
-                c.rigid_contact_new_count = torch.zeros(1, dtype=torch.int32, device=dev)
-                c.rigid_contact_broken_indices = torch.zeros(n, dtype=torch.int32, device=dev)
-                c.rigid_contact_broken_count = torch.zeros(1, dtype=torch.int32, device=dev)
-                c._report_buffers = (c.rigid_contact_new_indices, c.rigid_contact_new_count, c.rigid_contact_broken_indices,
-                                     c.rigid_contact_broken_count, torch.zeros(n, dtype=torch.int32, device=dev),  # scan flags, offsets
-                                     torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n // 1024 + 2, dtype=torch.int32, device=dev))
+            add_matching_buffers(c, self._rigid_contact_max, self.contact_report, self.dm.device)
         return c
 
     def reset_contact_matching(self, world_mask=None) -> None:

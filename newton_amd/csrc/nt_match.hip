@@ -375,9 +375,13 @@ __global__ void __launch_bounds__(ROW_WAVE) order_row_bucket_kernel(nt_model m, 
     }
 }
 
+__device__ inline int32_t global_id(const int32_t* gid, int32_t local) { return local >= 0 ? gid[local] : local; }
 __device__ inline void st3v(float* p, size_t i, float x, float y, float z) { p[3 * i] = x; p[3 * i + 1] = y; p[3 * i + 2] = z; }
 
-__global__ void __launch_bounds__(256) order_slot_scatter_kernel(nt_model m, nt_contacts c, nt_contact_order o, nt_sorted_contacts s) {
+// (GLOBAL_IDS: a world group's contacts written into the arrays of the whole heterogeneous model, shape ids through `gid`)
+template <bool GLOBAL_IDS>
+__global__ void __launch_bounds__(256) order_slot_scatter_kernel(nt_model m, nt_contacts c, nt_contact_order o, nt_sorted_contacts s,
+                                                                 const int32_t* gid) {
     const int E = m.env_count, ES = m.env_stride, cpp = m.cpp, ncs = m.np * cpp;
     const size_t n = (size_t)ncs * ES;
     for (size_t gi = (size_t)blockIdx.x * blockDim.x + threadIdx.x; gi < n; gi += (size_t)gridDim.x * blockDim.x) {
@@ -397,8 +401,8 @@ __global__ void __launch_bounds__(256) order_slot_scatter_kernel(nt_model m, nt_
         if (idx >= s.cap) continue;
         const float* D = c.data;
         auto ld = [&](int comp) { return D[((size_t)comp * ncs + slot) * ES + env]; };
-        s.shape0[idx] = s0;
-        s.shape1[idx] = c.shape1[gi];
+        s.shape0[idx] = GLOBAL_IDS ? gid[s0] : s0;
+        s.shape1[idx] = GLOBAL_IDS ? global_id(gid, c.shape1[gi]) : c.shape1[gi];
         st3v(s.point0, idx, ld(CD_POINT0), ld(CD_POINT0 + 1), ld(CD_POINT0 + 2));
         st3v(s.point1, idx, ld(CD_POINT1), ld(CD_POINT1 + 1), ld(CD_POINT1 + 2));
         st3v(s.offset0, idx, ld(CD_OFFSET0), ld(CD_OFFSET0 + 1), ld(CD_OFFSET0 + 2));
@@ -415,7 +419,9 @@ __global__ void __launch_bounds__(256) order_slot_scatter_kernel(nt_model m, nt_
     }
 }
 
-__global__ void __launch_bounds__(256) order_row_scatter_kernel(nt_model m, nt_flat_rows f, nt_contact_order o, nt_sorted_contacts s) {
+template <bool GLOBAL_IDS>
+__global__ void __launch_bounds__(256) order_row_scatter_kernel(nt_model m, nt_flat_rows f, nt_contact_order o, nt_sorted_contacts s,
+                                                                const int32_t* gid) {
     const int E = m.env_count;
     const int nf = f.row_start[E] < s.row_capacity ? f.row_start[E] : s.row_capacity;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < s.row_capacity; i += gridDim.x * blockDim.x) {
@@ -424,8 +430,8 @@ __global__ void __launch_bounds__(256) order_row_scatter_kernel(nt_model m, nt_f
         const int idx = o.bucket_start[b] + o.row_sub[i];
         s.row_flat[i] = idx;
         if (idx >= s.cap) continue;
-        s.shape0[idx] = f.shape0[i];
-        s.shape1[idx] = f.shape1[i];
+        s.shape0[idx] = GLOBAL_IDS ? global_id(gid, f.shape0[i]) : f.shape0[i];
+        s.shape1[idx] = GLOBAL_IDS ? global_id(gid, f.shape1[i]) : f.shape1[i];
         for (int k = 0; k < 3; ++k) {
             s.point0[3 * (size_t)idx + k] = f.point0[3 * (size_t)i + k];
             s.point1[3 * (size_t)idx + k] = f.point1[3 * (size_t)i + k];
@@ -579,11 +585,11 @@ nt_status nt_contacts_export_sorted(const nt_model* m, const nt_contacts* c, con
         return NT_ERR_LAUNCH;
     }
     if (slots)
-        hipLaunchKernelGGL(order_slot_scatter_kernel, dim3(grid_for((size_t)m->np * m->cpp * m->env_stride, 256)), dim3(256), 0, st,
-                           *m, *c, *o, *out);
+        hipLaunchKernelGGL(order_slot_scatter_kernel<false>, dim3(grid_for((size_t)m->np * m->cpp * m->env_stride, 256)), dim3(256), 0,
+                           st, *m, *c, *o, *out, (const int32_t*)nullptr);
     if (rows)
-        hipLaunchKernelGGL(order_row_scatter_kernel, dim3(grid_for((size_t)out->row_capacity, 256)), dim3(256), 0, st, *m, c->flat, *o,
-                           *out);
+        hipLaunchKernelGGL(order_row_scatter_kernel<false>, dim3(grid_for((size_t)out->row_capacity, 256)), dim3(256), 0, st, *m,
+                           c->flat, *o, *out, (const int32_t*)nullptr);
     hipLaunchKernelGGL(order_tail_kernel, dim3(grid_for((size_t)out->cap, 256)), dim3(256), 0, st, *out);
     return hipGetLastError() == hipSuccess ? NT_OK : NT_ERR_LAUNCH;
 }
@@ -625,6 +631,186 @@ nt_status nt_contacts_order_save(const nt_model* m, const nt_sorted_contacts* s,
     size_t n = nslot > (size_t)s->row_capacity ? nslot : (size_t)s->row_capacity;
     if (n < (size_t)m->env_count) n = (size_t)m->env_count;
     hipLaunchKernelGGL(order_save_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, *m, *s, *r);
+    return hipGetLastError() == hipSuccess ? NT_OK : NT_ERR_LAUNCH;
+}
+
+}  // extern "C"
+
+// ---- the same over the world groups of a heterogeneous model (nt_contact_group) -------------------------------------------------
+// Every per-group pass of the export indexes bucket_fill / bucket_start by rank only: with global ranks and the global scan arrays
+// the groups' count passes fill disjoint entries of one bucket_fill, one scan runs over all buckets and the groups' scatters write
+// disjoint ranges of one set of arrays.  The report / save passes that walk a group's slots or rows run per group; the ones over the
+// arrays (new flags, compaction, hit, scans) run once.
+namespace {
+
+// what the per-group passes see: the group's table on the global scan, the global arrays with the group's positions, the group's
+// matching state with the global outputs
+nt_contact_order group_order(const nt_contact_group& g, const nt_contact_order* o) {
+    nt_contact_order x = *g.o;
+    x.bucket_fill = o->bucket_fill;
+    x.bucket_start = o->bucket_start;
+    x.block_sum = o->block_sum;
+    return x;
+}
+nt_sorted_contacts group_sorted(const nt_contact_group& g, const nt_sorted_contacts* s) {
+    nt_sorted_contacts x = *s;
+    x.row_capacity = g.row_capacity;
+    x.slot_flat = g.slot_flat;
+    x.row_flat = g.row_flat;
+    return x;
+}
+nt_contact_report group_report(const nt_contact_group& g, const nt_contact_report* r) {
+    nt_contact_report x = *g.r;
+    x.prev_count = r->prev_count;
+    x.match_index = r->match_index;
+    x.new_indices = r->new_indices;
+    x.new_count = r->new_count;
+    x.broken_indices = r->broken_indices;
+    x.broken_count = r->broken_count;
+    x.flag = r->flag;
+    x.offset = r->offset;
+    x.block_sum = r->block_sum;
+    return x;
+}
+
+bool arrays_ok(const nt_sorted_contacts* s) {
+    return s && s->cap > 0 && s->count && s->shape0 && s->shape1 && s->point0 && s->point1 && s->offset0 && s->offset1 && s->normal &&
+           s->margin0 && s->margin1 && (!s->stiffness || (s->damping && s->friction));
+}
+bool group_ok(const nt_contact_group& g) {
+    const nt_model* m = g.m;
+    return m && g.c && g.o && m->env_count > 0 && g.row_capacity >= 0 && (m->np == 0 || g.slot_flat) &&
+           (g.row_capacity == 0 || g.row_flat);
+}
+// the group's matching state (report / save)
+bool group_report_ok(const nt_contact_group& g) {
+    const nt_contact_report* r = g.r;
+    if (!group_ok(g) || !r) return false;
+    if (g.m->np > 0 && (!r->prev_slot_flat || !r->slot_match || !r->prev_slot_live)) return false;
+    return g.row_capacity == 0 || (r->prev_row_flat && r->row_match && r->prev_row_live && r->prev_row_start && r->prev_pair_count);
+}
+
+}  // namespace
+
+extern "C" {
+
+nt_status nt_contacts_export_sorted_groups(int32_t group_count, const nt_contact_group* groups, const nt_contact_order* o,
+                                           nt_sorted_contacts* out, void* stream) {
+    if (group_count <= 0 || !groups || !o || !arrays_ok(out) || o->bucket_count < 0 || !o->bucket_fill || !o->bucket_start ||
+        !o->block_sum)
+        return NT_ERR_INVALID_ARG;
+    long long buckets = 0;
+    size_t row_lds_max = 0;
+    for (int i = 0; i < group_count; ++i) {
+        const nt_contact_group& g = groups[i];
+        if (!group_ok(g)) return NT_ERR_INVALID_ARG;
+        const nt_model* m = g.m;
+        const nt_contacts* c = g.c;
+        const nt_contact_order* go = g.o;
+        const int E = m->env_count;
+        const bool slots = m->np > 0, rows = g.row_capacity > 0;
+        if (slots && (!c->shape0 || !c->shape1 || !c->data || !go->tile_shape0 || !go->tile_rank || !g.shape_id)) return NT_ERR_INVALID_ARG;
+        if (rows && (!c->flat.row_start || !c->flat.shape0 || go->row_keys <= 0 || !go->row_key || !go->row_rank || !go->row_bucket ||
+                     !go->row_sub || !go->row_unmatched || !g.shape_id))
+            return NT_ERR_INVALID_ARG;
+        if (go->bucket_count != 2 * E * m->np + (rows ? E * go->row_keys : 0)) return NT_ERR_INVALID_ARG;
+        buckets += go->bucket_count;
+        const size_t row_lds = rows ? sizeof(int32_t) * ((size_t)go->row_keys + ROW_WAVE) : 0;
+        if (row_lds > row_lds_max) row_lds_max = row_lds;
+    }
+    if (buckets != o->bucket_count) return NT_ERR_INVALID_ARG;
+    if (row_lds_max > 64 * 1024) return NT_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    for (int i = 0; i < group_count; ++i) {  // counts: disjoint entries of the global bucket_fill
+        const nt_contact_group& g = groups[i];
+        const nt_model* m = g.m;
+        const nt_contact_order go = group_order(g, o);
+        const int E = m->env_count;
+        if (m->np > 0)
+            hipLaunchKernelGGL(order_tile_count_kernel, dim3(grid_for((size_t)m->np * E, 256)), dim3(256), 0, st, *m, *g.c, go);
+        if (g.row_capacity > 0)
+            hipLaunchKernelGGL(order_row_bucket_kernel, dim3(grid_for((size_t)E, 1)), dim3(ROW_WAVE),
+                               sizeof(int32_t) * ((size_t)go.row_keys + ROW_WAVE), st, *m, g.c->flat, g.row_capacity, go);
+    }
+    if (o->bucket_count > 0) {
+        launch_scan(o->bucket_fill, o->bucket_count, o->block_sum, o->bucket_start, out->count, st);
+    } else if (hipMemsetAsync(out->count, 0, sizeof(int32_t), st) != hipSuccess) {
+        return NT_ERR_LAUNCH;
+    }
+    for (int i = 0; i < group_count; ++i) {  // scatters: disjoint ranges of the global arrays
+        const nt_contact_group& g = groups[i];
+        const nt_model* m = g.m;
+        const nt_contact_order go = group_order(g, o);
+        const nt_sorted_contacts gs = group_sorted(g, out);
+        if (m->np > 0)
+            hipLaunchKernelGGL(order_slot_scatter_kernel<true>, dim3(grid_for((size_t)m->np * m->cpp * m->env_stride, 256)), dim3(256), 0,
+                               st, *m, *g.c, go, gs, g.shape_id);
+        if (g.row_capacity > 0)
+            hipLaunchKernelGGL(order_row_scatter_kernel<true>, dim3(grid_for((size_t)g.row_capacity, 256)), dim3(256), 0, st, *m,
+                               g.c->flat, go, gs, g.shape_id);
+    }
+    hipLaunchKernelGGL(order_tail_kernel, dim3(grid_for((size_t)out->cap, 256)), dim3(256), 0, st, *out);
+    return hipGetLastError() == hipSuccess ? NT_OK : NT_ERR_LAUNCH;
+}
+
+nt_status nt_contacts_match_report_groups(int32_t group_count, const nt_contact_group* groups, const nt_sorted_contacts* s,
+                                          const nt_contact_report* r, void* stream) {
+    if (group_count <= 0 || !groups || !arrays_ok(s) || !r || !r->prev_count || !r->match_index) return NT_ERR_INVALID_ARG;
+    const bool report = r->new_indices != nullptr;
+    if (report && (!r->new_count || !r->broken_indices || !r->broken_count || !r->flag || !r->offset || !r->block_sum))
+        return NT_ERR_INVALID_ARG;
+    for (int i = 0; i < group_count; ++i)
+        if (!group_report_ok(groups[i])) return NT_ERR_INVALID_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned gc = grid_for((size_t)s->cap, 256);
+    for (int i = 0; i < group_count; ++i) {  // each group's matches, through its previous positions (global) to global positions
+        const nt_contact_group& g = groups[i];
+        const nt_sorted_contacts gs = group_sorted(g, s);
+        const nt_contact_report gr = group_report(g, r);
+        if (g.m->np > 0)
+            hipLaunchKernelGGL(report_map_slots_kernel, dim3(grid_for((size_t)g.m->np * g.m->cpp * g.m->env_stride, 256)), dim3(256), 0,
+                               st, *g.m, gs, gr);
+        if (g.row_capacity > 0)
+            hipLaunchKernelGGL(report_map_rows_kernel, dim3(grid_for((size_t)g.row_capacity, 256)), dim3(256), 0, st, gs, gr);
+    }
+    hipLaunchKernelGGL(report_new_flags_kernel, dim3(gc), dim3(256), 0, st, *s, *r, report ? 1 : 0);
+    if (report) {
+        launch_scan(r->flag, s->cap, r->block_sum, r->offset, r->new_count, st);
+        hipLaunchKernelGGL(report_compact_kernel, dim3(gc), dim3(256), 0, st, s->cap, (const int32_t*)r->flag, (const int32_t*)r->offset,
+                           r->new_indices);
+        hipLaunchKernelGGL(report_clear_kernel, dim3(gc), dim3(256), 0, st, s->cap, r->flag);
+        for (int i = 0; i < group_count; ++i) {
+            const nt_contact_group& g = groups[i];
+            const nt_sorted_contacts gs = group_sorted(g, s);
+            const nt_contact_report gr = group_report(g, r);
+            if (g.m->np > 0)
+                hipLaunchKernelGGL(report_alive_slots_kernel, dim3(grid_for((size_t)g.m->np * g.m->cpp * g.m->env_stride, 256)), dim3(256),
+                                   0, st, *g.m, gs, gr);
+            if (g.row_capacity > 0)
+                hipLaunchKernelGGL(report_alive_rows_kernel, dim3(grid_for((size_t)g.row_capacity, 256)), dim3(256), 0, st, *g.m, gs, gr);
+        }
+        hipLaunchKernelGGL(report_hit_kernel, dim3(gc), dim3(256), 0, st, *s, *r);
+        launch_scan(r->flag, s->cap, r->block_sum, r->offset, r->broken_count, st);
+        hipLaunchKernelGGL(report_compact_kernel, dim3(gc), dim3(256), 0, st, s->cap, (const int32_t*)r->flag, (const int32_t*)r->offset,
+                           r->broken_indices);
+    }
+    return hipGetLastError() == hipSuccess ? NT_OK : NT_ERR_LAUNCH;
+}
+
+nt_status nt_contacts_order_save_groups(int32_t group_count, const nt_contact_group* groups, const nt_sorted_contacts* s,
+                                        const nt_contact_report* r, void* stream) {
+    if (group_count <= 0 || !groups || !arrays_ok(s) || !r || !r->prev_count) return NT_ERR_INVALID_ARG;
+    for (int i = 0; i < group_count; ++i)
+        if (!group_report_ok(groups[i])) return NT_ERR_INVALID_ARG;
+    for (int i = 0; i < group_count; ++i) {  // (every group's pass also writes the global count into r->prev_count)
+        const nt_contact_group& g = groups[i];
+        const nt_model* m = g.m;
+        const size_t nslot = (size_t)m->np * m->cpp * m->env_stride;
+        size_t n = nslot > (size_t)g.row_capacity ? nslot : (size_t)g.row_capacity;
+        if (n < (size_t)m->env_count) n = (size_t)m->env_count;
+        hipLaunchKernelGGL(order_save_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, *m, group_sorted(g, s),
+                           group_report(g, r));
+    }
     return hipGetLastError() == hipSuccess ? NT_OK : NT_ERR_LAUNCH;
 }
 

@@ -12,12 +12,17 @@ composites over the groups' objects:
 * ``collide`` / ``step`` / ``rollout`` issue one launch per group, each group on its own HIP stream forked from and joined
   back into the caller's stream (the groups are independent, and a small group does not fill 256 CUs on its own);
 * contact shape ids are translated back to the global model's shape ids, rows are the groups' rows in group order, which is
-  the reference's append order over the world-major candidate pairs.
+  the reference's append order over the world-major candidate pairs;
+* ``CollisionPipeline(deterministic=True)`` and contact matching work over the whole model: the flat arrays are that raw order
+  under one stable sort on (shape0 << 32 | shape1) in global ids, written on the device into persistent arrays after the groups'
+  launches join (``nt_contacts_export_sorted_groups``, include/newton_hip_contacts.h), and match indices / the new / broken
+  lists are global positions, each group keeping its own matcher -- such a ``collide()`` reads nothing back.
 
 Nothing here touches the arithmetic: a group of k identical worlds steps exactly like a k-world replicated model.
 """
 from __future__ import annotations
 
+import ctypes as C
 import functools
 
 import numpy as np
@@ -308,13 +313,59 @@ def _make_state_classes():
     return GroupedState, GroupedControl
 
 
+def grouped_contact_order_tables(model, with_rows):
+    """Global ranks of the key-ordered export over the world groups (nt_contact_group, include/newton_hip_contacts.h), built once
+    per heterogeneous model and row layout: every group's buckets (collide.contact_order_tables of its sub-model) keyed in GLOBAL
+    shape ids and enumerated in the raw heterogeneous order -- the analytic tile buckets of every group in group order, then per
+    group its convex tile buckets and its row buckets -- ranked by one stable argsort of the keys.  A group's local -> global id map
+    is increasing, so its own key order is kept.  `with_rows[g]`: group g's contacts carry the rows of an SDF / vertex leg.
+    -> {"bucket_count": B, "bucket_key": [B] key by global bucket id, "groups": [(tile_rank [P*E*2], row_rank [E, K], K)]}"""
+    from .collide import _tile_shape_ids, contact_order_tables  # noqa: PLC0415
+
+    key = tuple(bool(r) for r in with_rows)
+    cache = model.__dict__.setdefault("_grouped_contact_order", {})
+    if key in cache:
+        return cache[key]
+    first, second, layout, off = [], [], [], 0  # (keys, global bucket ids) per segment of the raw order
+    for part, rows in zip(model.world_groups.parts, key):
+        t, tab = part.env, contact_order_tables(part)
+        gid = np.asarray(part._global_shape_ids, np.int64)
+        E, P, npa = t.env_count, t.np, t.np_analytic
+        a, b = (gid[x] for x in _tile_shape_ids(t))
+        tile_key = np.stack([(a << 32) + b, (b << 32) + a], axis=-1)  # [P, E, 2]
+        ids = off + np.arange(P * E * 2).reshape(P, E, 2)
+        for (lo, hi), dst in (((0, npa), first), ((npa, P), second)):  # env-major, then pair, then orientation
+            dst.append((tile_key[lo:hi].transpose(1, 0, 2).reshape(-1), ids[lo:hi].transpose(1, 0, 2).reshape(-1)))
+        K = int(tab["row_keys"]) if rows else 0
+        if K:  # (the row keys stay group-local on the device: only their ranks are global)
+            rk = np.asarray(tab["row_key"], np.int64)
+            second.append((((gid[rk >> 32] << 32) + gid[rk & 0xFFFFFFFF]).reshape(-1), off + P * E * 2 + np.arange(E * K)))
+        layout.append((off, P * E * 2, E, K))
+        off += P * E * 2 + E * K
+    keys = np.concatenate([k for k, _ in first + second] + [np.zeros(0, np.int64)])
+    ids = np.concatenate([i for _, i in first + second] + [np.zeros(0, np.int64)])
+    rank = np.empty(off, np.int64)
+    rank[ids[np.argsort(keys, kind="stable")]] = np.arange(off)
+    bucket_key = np.empty(off, np.int64)
+    bucket_key[ids] = keys
+    out = {"bucket_count": off, "bucket_key": bucket_key,
+           "groups": [(rank[o:o + n].astype(np.int32), rank[o + n:o + n + E * K].reshape(E, K).astype(np.int32), K)
+                      for o, n, E, K in layout]}
+    cache[key] = out
+    return out
+
+
 class GroupedContacts:
     """Contacts of a heterogeneous model (contacts.py:227-277), shape ids of the global model.  Row order = the reference's
     append order: its primitive narrow-phase launch writes first and its MPR / GJK launch second (narrow_phase.py:458-1014,
     1221-1452), each over the world-major candidate pairs - so the analytic rows of every group in group order, then the
-    convex rows of every group (a group's own export already has this two-segment shape, nt_contacts_export)."""
+    convex rows of every group (a group's own export already has this two-segment shape, nt_contacts_export).
 
-    def __init__(self, model, parts):
+    With sort_by_key (CollisionPipeline(deterministic=True) or contact matching) the flat views are persistent arrays over the whole
+    model, written on the device by nt_contacts_export_sorted_groups: that raw order under a stable sort on (shape0 << 32 | shape1)
+    in global ids.  The groups' own Contacts stay raw."""
+
+    def __init__(self, model, parts, sort_by_key=False):
         self.model = model
         self.parts = parts
         self.rigid_contact_max = sum(c.rigid_contact_max for c in parts)
@@ -330,6 +381,131 @@ class GroupedContacts:
         self._gids = [torch.as_tensor(np.asarray(c.model._global_shape_ids), dtype=torch.int64, device=dev) for c in parts]
         self._seg_cache = (None, None)  # (generations, segments): one host sync per group and per collide, not per field read
         self._row_cache = {}
+        self.sort_by_key = bool(sort_by_key)
+        if self.sort_by_key:
+            self._init_sorted_export()
+
+    # -- key-ordered views over all groups (sort_by_key) ----------------------------------------------------------------------------
+    def _init_sorted_export(self):
+        """Allocate the global arrays, every group's positions and global-rank tables and the global scan once."""
+        from . import _lib  # noqa: PLC0415
+        from .collide import contact_order_tables  # noqa: PLC0415
+
+        torch = _torch()
+        parts = self.parts
+        dev, cap = parts[0]._shape0.device, max(self.rigid_contact_max, 1)
+        i32, f32 = torch.int32, torch.float32
+        e = {"count": torch.zeros(1, dtype=i32, device=dev),
+             "shape0": torch.full((cap,), -1, dtype=i32, device=dev), "shape1": torch.full((cap,), -1, dtype=i32, device=dev)}
+        for name in ("point0", "point1", "offset0", "offset1", "normal"):
+            e[name] = torch.zeros((cap, 3), dtype=f32, device=dev)
+        e["margin0"], e["margin1"] = torch.zeros(cap, dtype=f32, device=dev), torch.zeros(cap, dtype=f32, device=dev)
+        if any(c._prop is not None or (c._flat is not None and c._flat.stiffness is not None) for c in parts):
+            for name in ("stiffness", "damping", "friction"):
+                e[name] = torch.zeros(cap, dtype=f32, device=dev)
+        self._export, self._export_gen, self._order_cache, self._force = e, None, None, None
+        tab = grouped_contact_order_tables(self.model, [c._flat is not None for c in parts])
+        B = tab["bucket_count"]
+
+        def up(a, dtype):
+            a = np.ascontiguousarray(a)
+            return torch.from_numpy(a if a.size else np.zeros(1, a.dtype)).to(device=dev, dtype=dtype)
+
+        self._order_scratch = (torch.zeros(max(B, 1), dtype=i32, device=dev), torch.zeros(max(B, 1), dtype=i32, device=dev),
+                               torch.zeros(B // 1024 + 2, dtype=i32, device=dev))
+        self.order_unmatched_rows = torch.zeros(1, dtype=i32, device=dev)  # rows outside every bucket (stays 0)
+        o = _lib.nt_contact_order()
+        o.bucket_count = B
+        o.bucket_fill, o.bucket_start, o.block_sum = (x.data_ptr() for x in self._order_scratch)
+        self._order = o
+        so = _lib.nt_sorted_contacts()
+        so.cap = cap
+        for name, v in e.items():
+            setattr(so, name, v.data_ptr())
+        self._sorted = so
+        self._group_tabs = []  # per group: (nt_contact_order, slot_flat, row_flat, row capacity, tensors kept alive)
+        for c, (tile_rank, row_rank, K) in zip(parts, tab["groups"]):
+            t, ptab = c.model.env, contact_order_tables(c.model)
+            row_cap = c._flat.capacity if c._flat is not None else 0
+            slot_flat = torch.full((max(c._slots, 1), t.env_stride), -1, dtype=i32, device=dev)
+            row_flat = torch.full((max(row_cap, 1),), -1, dtype=i32, device=dev)
+            keep = (up(ptab["tile_shape0"], i32), up(tile_rank, i32), up(ptab["row_key"], torch.int64), up(row_rank, i32),
+                    up(c.model._global_shape_ids, i32), torch.zeros(max(row_cap, 1), dtype=i32, device=dev),
+                    torch.zeros(max(row_cap, 1), dtype=i32, device=dev))
+            go = _lib.nt_contact_order()
+            go.bucket_count, go.row_keys = 2 * t.env_count * t.np + t.env_count * K, K
+            go.tile_shape0, go.tile_rank, go.row_key, go.row_rank = (x.data_ptr() for x in keep[:4])
+            go.row_bucket, go.row_sub = keep[5].data_ptr(), keep[6].data_ptr()
+            go.row_unmatched = self.order_unmatched_rows.data_ptr()
+            self._group_tabs.append((go, slot_flat, row_flat, row_cap, keep))
+
+    def _group_descs(self, matchers=None):
+        """-> (nt_contact_group array, what it points to); `matchers`: the groups' ContactMatcher (report / save)."""
+        from . import _lib  # noqa: PLC0415
+
+        n = len(self.parts)
+        arr, keep = (_lib.nt_contact_group * n)(), []
+        for i, (c, (go, slot_flat, row_flat, row_cap, tabs)) in enumerate(zip(self.parts, self._group_tabs)):
+            d = c._desc()
+            keep.append(d)
+            g = arr[i]
+            g.m, g.c, g.o = C.pointer(c.model.device_model().desc), C.pointer(d), C.pointer(go)
+            g.shape_id, g.row_capacity = tabs[4].data_ptr(), row_cap
+            g.slot_flat, g.row_flat = slot_flat.data_ptr(), row_flat.data_ptr()
+            if matchers is not None:
+                r = matchers[i]._report_desc()
+                keep.append(r)
+                g.r = C.pointer(r)
+        return arr, keep
+
+    def _export_sorted(self):
+        """(Re)write the global key-ordered views from every group's slots and rows: device work only, no host read."""
+        from . import _lib  # noqa: PLC0415
+
+        dm = self.parts[0].model.device_model()
+        groups, _keep = self._group_descs()
+        _lib.check(dm.lib.nt_contacts_export_sorted_groups(len(self.parts), groups, C.byref(self._order), C.byref(self._sorted),
+                                                           dm.stream()), "nt_contacts_export_sorted_groups")
+        self._export_gen = tuple(c._generation for c in self.parts)
+        return self._export
+
+    def _exported(self):
+        """The global views, re-exported when a group's contacts changed since (a rollout, a graph replay, clear())."""
+        if self._export_gen == tuple(c._generation for c in self.parts):
+            return self._export
+        return self._export_sorted()
+
+    def export_order(self):
+        """Permutation from the raw heterogeneous order to the order of the rigid_contact_* arrays (None = identity).  Non-trivial
+        only with CollisionPipeline(deterministic=True).  (A query: it reads the count back.)"""
+        if not self.sort_by_key:
+            return None
+        e = self._exported()
+        if self._order_cache is not None and self._order_cache[1] == self._export_gen:
+            return self._order_cache[0]
+        torch = _torch()
+        n = min(int(e["count"].item()), max(self.rigid_contact_max, 1))
+        order = None
+        if n > 1:  # (the raw index of every slot / row, scattered to its sorted position)
+            order = torch.empty(n, dtype=torch.int64, device=e["count"].device)
+            first, second = [], []
+            for c, (_go, slot_flat, row_flat, row_cap, _k) in zip(self.parts, self._group_tabs):
+                t = c.model.env
+                E, nas = t.env_count, t.np_analytic * t.cpp
+                first.append(slot_flat[:nas, :E].T.reshape(-1))
+                second.append(slot_flat[nas:c._slots, :E].T.reshape(-1))
+                if row_cap:
+                    second.append(row_flat[:row_cap])
+            base = 0
+            for pos in first + second:
+                pos = pos[pos >= 0].to(torch.int64)
+                order[pos] = base + torch.arange(pos.numel(), device=pos.device)
+                base += int(pos.numel())
+        self._order_cache = (order, self._export_gen)
+        return order
+
+    def _sorted_view(self, name):
+        return self._exported()[name[len("rigid_contact_"):]]
 
     def _segments(self):
         """Per group (row count, analytic row count) of its current export."""
@@ -349,6 +525,8 @@ class GroupedContacts:
 
     @property
     def rigid_contact_count(self):
+        if self.sort_by_key:
+            return self._exported()["count"]
         torch = _torch()
         return torch.stack([c.rigid_contact_count.reshape(-1)[0] for c in self.parts]).sum().reshape(1).to(torch.int32)
 
@@ -371,7 +549,18 @@ class GroupedContacts:
 
     @staticmethod
     def _field(name, translate=False):
-        return property(lambda self: self._rows(lambda c: getattr(c, name), translate, key=name))
+        return property(lambda self: self._sorted_view(name) if self.sort_by_key else
+                        self._rows(lambda c: getattr(c, name), translate, key=name))
+
+    @staticmethod
+    def _sorted_field(name):
+        """per-contact overrides of the key-ordered views (None unless a group's contacts carry them)"""
+        def get(self):
+            if not self.sort_by_key:
+                raise AttributeError(name)
+            return self._exported().get(name[len("rigid_contact_"):])
+
+        return property(get)
 
     @property
     def rigid_contact_count_per_env(self):
@@ -381,7 +570,17 @@ class GroupedContacts:
     def force(self):
         if any(c.force is None for c in self.parts):
             return None
-        return self._rows(lambda c: c.force)
+        if not self.sort_by_key:
+            return self._rows(lambda c: c.force)
+        # the groups' forces in the raw order, permuted like the key-ordered views: force[i] is the force of contact i
+        raw, order = self._rows(lambda c: c.force), self.export_order()
+        if self._force is None:
+            torch = _torch()
+            self._force = torch.zeros((max(self.rigid_contact_max, 1), 6), dtype=raw.dtype, device=raw.device)
+        n = int(raw.shape[0])
+        self._force.zero_()
+        self._force[:n] = raw if order is None else raw[order]
+        return self._force
 
     def clear(self):
         for c in self.parts:
@@ -396,40 +595,110 @@ GroupedContacts.rigid_contact_shape0 = GroupedContacts._field("rigid_contact_sha
 GroupedContacts.rigid_contact_shape1 = GroupedContacts._field("rigid_contact_shape1", True)
 for _n in ("point0", "point1", "offset0", "offset1", "normal", "margin0", "margin1"):
     setattr(GroupedContacts, "rigid_contact_" + _n, GroupedContacts._field("rigid_contact_" + _n))
+for _n in ("stiffness", "damping", "friction"):
+    setattr(GroupedContacts, "rigid_contact_" + _n, GroupedContacts._sorted_field("rigid_contact_" + _n))
 
 
 class GroupedCollisionPipeline:
-    """CollisionPipeline over the world groups (collide.py:1765-2207: one collide() per frame on the whole model)."""
+    """CollisionPipeline over the world groups (collide.py:1765-2207: one collide() per frame on the whole model).
+
+    Every group runs a default pipeline of its own (raw contacts).  deterministic=True and contact matching are served over the
+    whole model: each group keeps its own ContactMatcher (histories, sticky replay; a pair never spans two groups), and after the
+    groups' launches have joined the caller's stream the key-ordered export, the report and the save run once over all groups
+    (nt_contacts_export_sorted_groups / _match_report_groups / _order_save_groups): match indices are global positions."""
 
     def __init__(self, cls, model, **kwargs):
+        from .collide import ContactMatcher, check_matching_options  # noqa: PLC0415
+
         self.model = model
         self.groups: WorldGroups = model.world_groups
         if kwargs.get("rigid_contact_max") is not None:
             raise NotImplementedError("heterogeneous worlds: rigid_contact_max is derived per world group")
-        # a group's sorted export is group-local: with a world -1 shape (ground plane) in the pairs its rows would sit inside
-        # every group instead of in one global (shape0, shape1) block, and match indices would be group-local row numbers
-        for opt, off in (("deterministic", False), ("contact_matching", "disabled"), ("contact_report", False)):
-            if kwargs.get(opt, off) != off:
-                raise NotImplementedError(f"heterogeneous worlds: CollisionPipeline({opt}=...) is not supported; build the worlds "
-                                          "with one topology (ModelBuilder.replicate) to use it")
+        deterministic = bool(kwargs.pop("deterministic", False))
+        mode, report = kwargs.pop("contact_matching", "disabled"), bool(kwargs.pop("contact_report", False))
+        pos = kwargs.pop("contact_matching_pos_threshold", 0.0005)
+        dot = kwargs.pop("contact_matching_normal_dot_threshold", 0.995)
+        check_matching_options(mode, pos, dot, report)
         self.groups.sync_host()
         self.parts = [cls(p, **kwargs) for p in self.groups.parts]
-        self.deterministic = self.parts[0].deterministic
+        if mode != "disabled" and any(p._sdf_leg is not None and p._sdf_leg.has_hydro_pairs for p in self.parts):
+            # the reference matcher does not cover hydroelastic contacts either (contact_match.py:497-501)
+            raise NotImplementedError("contact_matching is not supported for hydroelastic contact pairs")
+        self.contact_matching, self.contact_report = mode, report
+        self.deterministic = deterministic or mode != "disabled"
+        self._matchers, self._prev_count = None, None
+        if mode != "disabled":
+            torch = _torch()
+            self._matchers = [ContactMatcher(p.model, pos, dot, sticky=mode == "sticky", sdf_leg=p._sdf_leg) for p in self.parts]
+            self._prev_count = torch.zeros(1, dtype=torch.int32, device=self.parts[0].dm.device)  # the previous frame's global count
 
     @property
     def rigid_contact_max(self):
         return sum(p.rigid_contact_max for p in self.parts)
 
     def contacts(self, **kwargs):
-        return GroupedContacts(self.model, [p.contacts(**kwargs) for p in self.parts])
+        c = GroupedContacts(self.model, [p.contacts(**kwargs) for p in self.parts], sort_by_key=self.deterministic)
+        c._contact_matching_mode = self.contact_matching
+        if self._matchers is not None:
+            from .collide import add_matching_buffers  # noqa: PLC0415
+
+            add_matching_buffers(c, c.rigid_contact_max, self.contact_report, self.parts[0].dm.device)
+        return c
 
     def reset_contact_matching(self, world_mask=None):
+        if self._matchers is None:
+            if world_mask is not None:
+                _split_world_mask(world_mask, self.groups)
+            raise ValueError('reset_contact_matching requires contact_matching != "disabled"')
         masks = _split_world_mask(world_mask, self.groups)
-        for i, p in enumerate(self.parts):
-            p.reset_contact_matching(None if masks is None else masks[i])
+        for i, mt in enumerate(self._matchers):
+            mt.reset(None if masks is None else masks[i])
+        if world_mask is None:
+            self._prev_count.zero_()
 
     def collide(self, state, contacts, **kwargs):
-        self.groups.run(lambda i, _p: self.parts[i].collide(state.parts[i], contacts.parts[i], **kwargs))
+        if not self.deterministic:
+            self.groups.run(lambda i, _p: self.parts[i].collide(state.parts[i], contacts.parts[i], **kwargs))
+            return
+        if not getattr(contacts, "sort_by_key", False):
+            raise ValueError("CollisionPipeline(deterministic=True) needs its own Contacts: use pipeline.contacts()")
+        mts = self._matchers
+        if mts is not None and getattr(contacts, "rigid_contact_match_index", None) is None:
+            raise ValueError("CollisionPipeline has contact_matching enabled but the Contacts buffer was created without it. "
+                             "Use pipeline.contacts() to create a compatible buffer.")
+
+        def go(i, _p):  # per group, on its stream: collide, then its matcher (previous SLOT / ROW per contact) [+ sticky replay]
+            s, c = state.parts[i], contacts.parts[i]
+            self.parts[i].collide(s, c, **kwargs)
+            if mts is not None:
+                mts[i]._match_kernels(s, c)
+                if mts[i].sticky:
+                    mts[i].replay_matched(s, c)
+
+        self.groups.run(go)
+        # joined: the global views (after the replay: the geometry the solver sees), then the report and the save over all groups
+        contacts._export_sorted()
+        if mts is not None:
+            self._report_and_save(state, contacts)
+
+    def _report_and_save(self, state, contacts):
+        from . import _lib  # noqa: PLC0415
+
+        mts = self._matchers
+        dm = self.parts[0].dm
+        r = _lib.nt_contact_report()
+        r.prev_count, r.match_index = self._prev_count.data_ptr(), contacts.rigid_contact_match_index.data_ptr()
+        if contacts._report_buffers is not None:  # (new_indices, new_count, broken_indices, broken_count, flag, offset, block_sum)
+            (r.new_indices, r.new_count, r.broken_indices, r.broken_count, r.flag, r.offset,
+             r.block_sum) = (x.data_ptr() for x in contacts._report_buffers)
+        groups, _keep = contacts._group_descs(mts)
+        n = len(self.parts)
+        _lib.check(dm.lib.nt_contacts_match_report_groups(n, groups, C.byref(contacts._sorted), C.byref(r), dm.stream()),
+                   "nt_contacts_match_report_groups")
+        for i, mt in enumerate(mts):  # (the report read the histories of the previous frame: save them only now)
+            mt._save_history(state.parts[i], contacts.parts[i])
+        _lib.check(dm.lib.nt_contacts_order_save_groups(n, groups, C.byref(contacts._sorted), C.byref(r), dm.stream()),
+                   "nt_contacts_order_save_groups")
 
 
 class GroupedSolver:
