@@ -8,6 +8,7 @@
  *   nt_semi_implicit_step <- SolverSemiImplicit.step(...)                        newton/_src/solvers/semi_implicit/solver_semi_implicit.py:123-217
  *   nt_xpbd_rollout       <- the CUDA-graph-captured simulate() loop             newton/examples/basic/example_basic_urdf.py:117-141
  *                            (clear_forces + collide + step + swap, N substeps, one launch)
+ *   nt_semi_implicit_rollout <- the same loop with SolverSemiImplicit.step, N substeps, one launch
  *   nt_clear_forces       <- State.clear_forces()                                newton/_src/sim/state.py:189-200
  *   nt_eval_fk            <- newton.eval_fk(model, joint_q, joint_qd, state)     newton/_src/sim/articulation.py:500-573
  *   nt_pack_aos / nt_unpack_aos <- the implicit AoS wp.array views of Model/State/Contacts
@@ -258,6 +259,13 @@ nt_status nt_xpbd_step(const nt_model* m, const nt_xpbd_params* p, nt_state* s_i
 nt_status nt_semi_implicit_step(const nt_model* m, const nt_semi_implicit_params* p, nt_state* s_in, nt_state* s_out,
                                 const nt_control* ctrl, const nt_contacts* c /*nullable*/, float dt,
                                 int32_t envs_per_block, void* stream);
+/* substeps x {clear_forces; collide; semi-implicit step; swap} in one launch, bitwise equal to the call-by-call loop: the result
+ * is in s0 when substeps is even, s1 when odd (the other state's body_q / body_qd are not written); body_f of both states is zeroed;
+ * c holds the contacts of the last substep's collide; joint_q / joint_qd are not touched.  cp nullable (envs_per_block 0 = auto).
+ * substeps <= 0: NT_ERR_INVALID_ARG; models with contact_scratch_in_hbm: NT_ERR_UNSUPPORTED (like nt_semi_implicit_step). */
+nt_status nt_semi_implicit_rollout(const nt_model* m, const nt_semi_implicit_params* p, const nt_collide_params* cp,
+                                   nt_state* s0, nt_state* s1, const nt_control* ctrl, nt_contacts* c, float dt,
+                                   int32_t substeps, void* stream);
 /* SolverFeatherstone.step (newton/_src/solvers/featherstone/solver_featherstone.py:462-1066): advances joint_q / joint_qd and
  * rebuilds body_q / body_qd of s_out; like the reference it also refreshes s_in->body_q from s_in->joint_q (FK).
  * Scope: PRISMATIC, REVOLUTE, BALL, FIXED, root FREE, D6 with <= 1 angular axis; child body of env-local joint j is body j. */

@@ -358,6 +358,9 @@ SYMBOLS = {
     "nt_semi_implicit_step": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_semi_implicit_params), C.POINTER(nt_state),
                                            C.POINTER(nt_state), C.POINTER(nt_control), C.POINTER(nt_contacts), C.c_float,
                                            C.c_int32, _P]),
+    "nt_semi_implicit_rollout": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_semi_implicit_params), C.POINTER(nt_collide_params),
+                                              C.POINTER(nt_state), C.POINTER(nt_state), C.POINTER(nt_control),
+                                              C.POINTER(nt_contacts), C.c_float, C.c_int32, _P]),
     "nt_featherstone_step": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_featherstone_params), C.POINTER(nt_state),
                                           C.POINTER(nt_state), C.POINTER(nt_control), C.POINTER(nt_contacts), C.c_float,
                                           C.c_int32, _P]),

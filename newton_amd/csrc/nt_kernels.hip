@@ -575,6 +575,58 @@ nt_status nt_semi_implicit_step(const nt_model* m, const nt_semi_implicit_params
 #endif
 }
 
+nt_status nt_semi_implicit_rollout(const nt_model* m, const nt_semi_implicit_params* p, const nt_collide_params* cp, nt_state* s0,
+                                   nt_state* s1, const nt_control* ctrl, nt_contacts* c, float dt, int32_t substeps, void* stream) {
+    if (!model_ok(m) || !p || !s0 || !s1 || !ctrl || !c || !s0->body_q || !s0->body_qd || !s0->body_f || !s1->body_q || !s1->body_qd ||
+        !s1->body_f || substeps <= 0)
+        return NT_ERR_INVALID_ARG;
+    KArgs a = {};
+    a.m = *m;
+    a.s_in = *s0;
+    a.s_out = *s1;
+    a.c = *ctrl;
+    a.ct = *c;
+    a.has_contacts = m->np > 0 ? 1 : 0;
+    a.sp = *p;
+    a.angular_damping = p->angular_damping;
+    a.dt = dt;
+    a.substeps = substeps;
+    if (m->contact_scratch_in_hbm) return NT_ERR_UNSUPPORTED;  // XPBD / collide only
+#ifdef NT_DEV_FAST
+    return NT_ERR_UNSUPPORTED;
+#else
+    int epb = pick_epb(*m, cp ? cp->envs_per_block : 0);
+    if (!epb) return NT_ERR_UNSUPPORTED;
+    const bool cvx = m->np_analytic < m->np;
+    if (epb == 4) epb = 8;
+    if (cvx && epb > 16) epb = 16;  // the convex variants are only instantiated for 1 / 8 / 16 envs per workgroup (build time)
+    // host twin of the kernel's tile (place_semi_rollout): wrench records or collide scratch, whichever is larger, behind the
+    // persistent block -- heavier than the collide / XPBD tile when the records dominate: narrow it like nt_semi_implicit_step does
+    LdsLayout L = make_layout(*m, false, false, false, false);
+    const size_t row_bytes = (size_t)place_semi_rollout(L, *m) * 4, shared_bytes = (size_t)topo_ints(*m) * 4;
+    while (epb > 8 && row_bytes * epb + shared_bytes > LDS_BYTES_PER_CU) epb /= 2;
+    if (row_bytes * epb + shared_bytes > LDS_BYTES_PER_CU) epb = 1;
+    const size_t lds_bytes = row_bytes * epb + shared_bytes;
+    if (lds_bytes > LDS_BYTES_PER_CU) return NT_ERR_UNSUPPORTED;
+    a.nslot = slots_for(*m, epb, max_threads_for(epb));
+    const int threads = ((a.nslot * epb + 63) / 64) * 64, blocks = (m->env_count + epb - 1) / epb;
+    auto go = [&](auto kernel) -> nt_status {
+        if (lds_bytes > 48 * 1024 &&
+            hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
+            return NT_ERR_LAUNCH;
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), lds_bytes, (hipStream_t)stream, a);
+        return hipGetLastError() == hipSuccess ? NT_OK : NT_ERR_LAUNCH;
+    };
+    if (cvx)
+        return epb == 16 ? go(semi_implicit_rollout_kernel<16, true>)
+             : epb == 8 ? go(semi_implicit_rollout_kernel<8, true>) : go(semi_implicit_rollout_kernel<1, true>);
+    return epb == 64 ? go(semi_implicit_rollout_kernel<64, false>)
+         : epb == 32 ? go(semi_implicit_rollout_kernel<32, false>)
+         : epb == 16 ? go(semi_implicit_rollout_kernel<16, false>)
+         : epb == 8 ? go(semi_implicit_rollout_kernel<8, false>) : go(semi_implicit_rollout_kernel<1, false>);
+#endif
+}
+
 #ifdef NT_PHASE_TIMING
 // debug build only: read and reset the phase cycle counters
 int nt_debug_phase_clocks(unsigned long long* out) {

@@ -164,6 +164,19 @@ inline LdsLayout make_layout_host(const nt_model& m, bool restitution = false, b
     return make_layout(m, m.contact_scratch_in_hbm != 0, restitution, uni, true, opts, big_lanes);
 }
 
+// SolverSemiImplicit's fused rollout (semi_implicit_rollout_kernel; host twin: nt_semi_implicit_rollout): the step kernel's tile --
+// persistent block | si_bf | si_jf | si_cw -- with the collide scratch laid over the wrench records.  The two never live together: the
+// collide phases of a substep end (barrier) before its force phase writes the first wrench, and what the fused contact lanes read of
+// the collide result is L.pm in the persistent block and the records in nt_contacts; the integrator has read the last wrench (barrier)
+// before the next substep's shape phase writes the scratch.  si_bf stays outside the union: it holds the zero body_f of clear_forces
+// for the whole launch.  L: a layout built with live_list = false (what Ctx builds for a solver's own row count).  Returns the rows
+// per environment.
+__host__ __device__ inline int place_semi_rollout(LdsLayout& L, const nt_model& m) {
+    const int coll = place_collide_scratch(L, m, L.si_jf.off, false);
+    const int wrenches = 13 * m.nj + NC_CW * m.np * m.cpp;
+    return L.si_jf.off + imax(imax(coll, wrenches), NT_MIN_SCRATCH_ROWS);
+}
+
 // the pre-step state snapshot (and the wide contact records) exist for restitution and for velocities from position deltas
 __host__ __device__ inline bool xpbd_keeps_prestep_state(const nt_xpbd_params& p) {
     return p.enable_restitution != 0 || p.compute_body_velocity_from_position_delta != 0;

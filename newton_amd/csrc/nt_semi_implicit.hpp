@@ -298,4 +298,49 @@ __global__ void __launch_bounds__(EPB <= 8 ? 256 : 512) semi_implicit_step_kerne
     __syncthreads();
     store_state(c, a.s_out);
 }
+
+// substeps x { clear_forces; CollisionPipeline.collide; SolverSemiImplicit.step; swap } in one launch: body state, parameters and
+// controls stay in LDS for the whole launch, the contact records go through nt_contacts in HBM once per substep (written by the pair
+// lanes, read by the contact lanes of the same workgroup behind do_collide's last barrier), and the Contacts buffers hold the last
+// substep's collide when the launch ends.  The phases are the ones of collide_kernel and semi_implicit_step_kernel in their order, the
+// body lanes sum the wrench records of every slot in index order like the step kernel: bitwise equal to the call-by-call loop.
+// The result lands in s_in (= s0) for an even number of substeps and in s_out (= s1) for an odd one; body_f of both is zeroed.
+// Tile: place_semi_rollout (nt_layout.hpp) -- the collide scratch shares its rows with the wrench records.
+template <int EPB, bool CVX>
+__global__ void __launch_bounds__(EPB <= 8 ? 256 : 512) semi_implicit_rollout_kernel(KArgs a) {
+    extern __shared__ __align__(16) float lds[];
+    const nt_model& m = a.m;
+    LdsLayout L0 = make_layout(m, false, false, false, false);
+    Ctx<EPB> c(a, lds, place_semi_rollout(L0, m));
+    place_semi_rollout(c.L, m);
+    c.L.bf = c.L.si_bf;
+    load_state(c, a.s_in);
+    load_params(c, true);
+    if (c.valid)
+        for (int r = c.slot; r < 6 * m.nb; r += c.nslot) {  // clear_forces: both states in HBM, and the staged body_f of every substep
+            a.s_in.body_f[(size_t)r * c.ES + c.env] = 0.0f;
+            a.s_out.body_f[(size_t)r * c.ES + c.env] = 0.0f;
+            c.l(c.L.bf, r / m.nb, m.nb, r % m.nb) = 0.0f;
+        }
+    __syncthreads();
+    stage_global_world(c);  // (static shapes: transform + AABB once per launch; the first pair phase is a barrier away)
+    c.gworld_ready = true;
+    Ctx<EPB> ci = c;  // the integrator reads joint wrenches through L.jf: alias it to the semi-implicit region
+    ci.L.jf = c.L.si_jf;
+    const int ncs = a.has_contacts ? m.np * m.cpp : 0;
+    const int spw = 64 / EPB > 0 ? 64 / EPB : 1;  // contact items start on a wave boundary (no mixed-path wave)
+    const int C0 = ((m.nj + spw - 1) / spw) * spw;
+    for (int s = 0; s < a.substeps; ++s) {
+        do_collide<EPB, CVX>(c, s == a.substeps - 1);
+        if (c.valid)
+            for (int i = c.slot; i < C0 + ncs; i += c.nslot) {
+                if (i < m.nj) si_joint_item(c, i);
+                else if (i >= C0) si_contact_item<EPB, true>(c, i - C0);
+            }
+        __syncthreads();
+        phase_integrate<EPB, true>(ci);
+        __syncthreads();  // (the next substep's shape phase overwrites the wrench records)
+    }
+    store_state(c, (a.substeps & 1) ? a.s_out : a.s_in);
+}
 #endif

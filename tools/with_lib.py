@@ -27,7 +27,7 @@ def main():
     # a variant built from older sources may lack entry points added since (measurement aids only): drop them from the loader's table
     # (looked up in the file, not by loading it: the library must be loaded AFTER torch so that both share one HIP runtime)
     blob = open(lib, "rb").read()
-    for name in ("nt_bandwidth_probe",):
+    for name in ("nt_bandwidth_probe", "nt_semi_implicit_rollout"):
         if name.encode() not in blob:
             _lib.SYMBOLS.pop(name, None)
     if sys.argv[2] == "-m":
