@@ -11,16 +11,10 @@ static nt_status fs_launch(const nt_model* m, KArgs& a, int32_t envs_per_block, 
 #ifdef NT_DEV_FAST
     return NT_ERR_UNSUPPORTED;
 #else
-#ifdef NT_ABLATION
-    {
-        const char* e = getenv("NT_DEBUG_SKIP");
-        a.debug_skip = e ? atoi(e) : 0;
-    }
-#endif
     const bool tree = fs_tree_mode(a);  // (a.fp is set by the caller: the layout of the launch follows the mass-matrix mode)
     FsLayout F = make_fs_layout(*m, make_layout(*m, false, false, false, false), tree);
     const size_t shared_ints = (size_t)topo_ints(*m) + fs_topo_ints(*m);
-    auto fits = [&](int epb) { return (size_t)F.rows * 4 * epb + shared_ints * 4 <= LDS_BYTES_PER_CU; };
+    auto fits = [&](int epb) { return tile_bytes(F.rows, epb, shared_ints) <= LDS_BYTES_PER_CU; };
     const bool cvx = m->np_analytic < m->np;
     // Uniform-parameter tile of 16 (round 6): the level-synchronous phases of this solver keep a handful of lanes per environment busy
     // and wait on LDS round trips and barriers, so what a CU delivers is the number of environments it holds.  With ONE block-shared
@@ -31,7 +25,7 @@ static nt_status fs_launch(const nt_model* m, KArgs& a, int32_t envs_per_block, 
     // (automatic from 2 049 environments: up to 2 048 the tiles of 4 are ONE round of 512 workgroups already and keep all 64 lanes per
     // environment -- 37.6 vs 32.6 M env-steps/s, profiles/r06H_ab_workloads.txt; envs_per_block = 16 asks for it at any size)
     const bool uni16 = rollout && !cvx && m->params_uniform && (envs_per_block == 16 || (envs_per_block == 0 && m->env_count > 2048)) &&
-                       (size_t)Fu.rows * 4 * 16 + shared_ints * 4 + (size_t)Lu.uni_floats * 4 <= LDS_BYTES_PER_CU;
+                       tile_bytes(Fu.rows, 16, shared_ints, Lu.uni_floats) <= LDS_BYTES_PER_CU;
     int epb = 0;
     if (uni16) {
         epb = 16;
@@ -51,32 +45,15 @@ static nt_status fs_launch(const nt_model* m, KArgs& a, int32_t envs_per_block, 
     const int max_threads = uni16 ? 512 : 256;
     int cap = max_threads / epb;
     a.nslot = want < cap ? want : cap;
-    int threads = ((a.nslot * epb + 63) / 64) * 64;
-    if (uni16) F = Fu;
-    size_t lds_bytes = (size_t)F.rows * 4 * epb + shared_ints * 4 + (uni16 ? (size_t)Lu.uni_floats * 4 : 0);
-    int blocks = (m->env_count + epb - 1) / epb;
-    auto go = [&](auto kernel) -> nt_status {
-        if (lds_bytes > 48 * 1024 &&
-            hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
-            return NT_ERR_LAUNCH;
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), lds_bytes, stream, a);
-        return hipGetLastError() == hipSuccess ? NT_OK : NT_ERR_LAUNCH;
-    };
-    if (uni16) return go(featherstone_rollout_kernel<16 + NT_UNI, false, 512>);
-    if (!rollout) {
-        if (epb == 16) return go(featherstone_step_kernel<16>);
-        if (epb == 8) return go(featherstone_step_kernel<8>);
-        if (epb == 4) return go(featherstone_step_kernel<4>);
-        return go(featherstone_step_kernel<1>);
-    }
-    if (cvx) {
-        if (epb == 8) return go(featherstone_rollout_kernel<8, true>);
-        return epb == 4 ? go(featherstone_rollout_kernel<4, true>) : go(featherstone_rollout_kernel<1, true>);
-    }
-    if (epb == 16) return go(featherstone_rollout_kernel<16, false>);
-    if (epb == 8) return go(featherstone_rollout_kernel<8, false>);
-    if (epb == 4) return go(featherstone_rollout_kernel<4, false>);
-    return go(featherstone_rollout_kernel<1, false>);
+    const size_t lds_bytes = uni16 ? tile_bytes(Fu.rows, 16, shared_ints, Lu.uni_floats) : tile_bytes(F.rows, epb, shared_ints);
+    if (uni16) return launch_tile(featherstone_rollout_kernel<16 + NT_UNI, false, 512>, a, 16, lds_bytes, stream);
+    if (!rollout)
+        return dispatch_epb(Epbs<16, 8, 4, 1>{}, epb, [&](auto E) { return launch_tile(featherstone_step_kernel<E>, a, E, lds_bytes, stream); });
+    if (cvx)
+        return dispatch_epb(Epbs<8, 4, 1>{}, epb,
+                            [&](auto E) { return launch_tile(featherstone_rollout_kernel<E, true>, a, E, lds_bytes, stream); });
+    return dispatch_epb(Epbs<16, 8, 4, 1>{}, epb,
+                        [&](auto E) { return launch_tile(featherstone_rollout_kernel<E, false>, a, E, lds_bytes, stream); });
 #endif
 }
 
@@ -140,24 +117,13 @@ nt_status nt_eval_fk(const nt_model* m, const float* joint_q, const float* joint
     int epb = 0;
     const int cands[4] = {16, 8, 4, 1};
     for (int i = 0; i < 4 && !epb; ++i)
-        if ((size_t)F.rows * 4 * cands[i] + shared_ints * 4 <= LDS_BYTES_PER_CU) epb = cands[i];
+        if (tile_bytes(F.rows, cands[i], shared_ints) <= LDS_BYTES_PER_CU) epb = cands[i];
     if (!epb) return NT_ERR_UNSUPPORTED;
     int want = imax(m->nb, m->nj), cap = 256 / epb;
     a.nslot = want < cap ? want : cap;
-    int threads = ((a.nslot * epb + 63) / 64) * 64;
-    size_t lds_bytes = (size_t)F.rows * 4 * epb + shared_ints * 4;
-    int blocks = (m->env_count + epb - 1) / epb;
-    auto go = [&](auto kernel) -> nt_status {
-        if (lds_bytes > 48 * 1024 &&
-            hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
-            return NT_ERR_LAUNCH;
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), lds_bytes, (hipStream_t)stream, a, joint_q, joint_qd);
-        return hipGetLastError() == hipSuccess ? NT_OK : NT_ERR_LAUNCH;
-    };
-    if (epb == 16) return go(eval_fk_kernel<16>);
-    if (epb == 8) return go(eval_fk_kernel<8>);
-    if (epb == 4) return go(eval_fk_kernel<4>);
-    return go(eval_fk_kernel<1>);
+    return dispatch_epb(Epbs<16, 8, 4, 1>{}, epb, [&](auto E) {
+        return launch_tile(eval_fk_kernel<E>, a, E, tile_bytes(F.rows, E, shared_ints), (hipStream_t)stream, joint_q, joint_qd);
+    });
 #endif
 }
 

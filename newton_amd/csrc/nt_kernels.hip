@@ -199,7 +199,7 @@ int slots_for(const nt_model& m, int epb, int max_threads) {
 
 size_t tile_lds_bytes(const nt_model& m, int epb, bool restitution, bool uni) {
     LdsLayout L = make_layout_host(m, restitution, uni);
-    return (size_t)L.rows_per_env * 4 * epb + (size_t)topo_ints(m) * 4 + (size_t)L.uni_floats * 4;
+    return tile_bytes(L.rows_per_env, epb, topo_ints(m), L.uni_floats);
 }
 bool epb_fits(const nt_model& m, int epb, bool restitution = false, bool uni = false) {
     return tile_lds_bytes(m, epb, restitution, uni) <= LDS_BYTES_PER_CU;
@@ -209,7 +209,7 @@ bool epb_fits(const nt_model& m, int epb, bool restitution = false, bool uni = f
 bool big_wide_fits(const nt_model& m, bool restitution) {
     if (!m.contact_scratch_in_hbm || m.np_analytic == m.np) return false;  // (only the convex kernels carry the wide form)
     LdsLayout L = make_layout_host(m, restitution, false, 0, NT_BIG_SCENE_LANES_WIDE);
-    return (size_t)L.rows_per_env * 4 + (size_t)topo_ints(m) * 4 <= LDS_BYTES_PER_CU;
+    return tile_bytes(L.rows_per_env, 1, topo_ints(m)) <= LDS_BYTES_PER_CU;
 }
 
 int pick_epb(const nt_model& m, int requested, bool restitution = false) {
@@ -232,48 +232,66 @@ int pick_epb(const nt_model& m, int requested, bool restitution = false) {
     return epb_fits(m, 1, restitution) ? 1 : 0;
 }
 
+// the wrench records of SolverSemiImplicit (`rows` per environment: its step or its rollout tile) can make its tile heavier than the
+// collide / XPBD one: halve a wide tile until it fits the CU, else one environment per workgroup
+int narrow_semi_epb(const nt_model& m, int epb, int rows) {
+    while (epb > 8 && tile_bytes(rows, epb, topo_ints(m)) > LDS_BYTES_PER_CU) epb /= 2;
+    return tile_bytes(rows, epb, topo_ints(m)) > LDS_BYTES_PER_CU ? 1 : epb;
+}
+
 // semi: the SolverSemiImplicit kernel (own scratch layout); max_threads: the kernel's THREADS template argument
 // a.tile_opts on entry: the NT_TILE_* layout extras the kernel can use (nt_xpbd_rollout asks); granted only while the tile still fits
 // the CU, and the kernel sees what was granted
 template <typename K>
 nt_status launch(K kernel, KArgs a, int epb, hipStream_t stream, int max_threads = 0, bool semi = false, bool uni = false) {
     int tile_opts = a.tile_opts;
-    auto tile_bytes = [&](int opts) {
+    auto opts_bytes = [&](int opts) {
         LdsLayout Lo = make_layout_host(a.m, xpbd_keeps_prestep_state(a.p), uni, opts, NT_BIG_SCENE_LANES);
-        return (size_t)Lo.rows_per_env * 4 * epb + (size_t)topo_ints(a.m) * 4 + (size_t)Lo.uni_floats * 4;
+        return tile_bytes(Lo.rows_per_env, epb, topo_ints(a.m), Lo.uni_floats);
     };
     if (semi) tile_opts = 0;
     if ((tile_opts & NT_TILE_LDS_RECORDS) &&
-        (a.m.np_analytic != a.m.np || a.m.contact_scratch_in_hbm || xpbd_keeps_prestep_state(a.p) || tile_bytes(tile_opts) > LDS_BYTES_PER_CU))
+        (a.m.np_analytic != a.m.np || a.m.contact_scratch_in_hbm || xpbd_keeps_prestep_state(a.p) || opts_bytes(tile_opts) > LDS_BYTES_PER_CU))
         tile_opts &= ~NT_TILE_LDS_RECORDS;
-    if (tile_bytes(tile_opts) > LDS_BYTES_PER_CU) tile_opts = 0;
+    if (opts_bytes(tile_opts) > LDS_BYTES_PER_CU) tile_opts = 0;
     a.tile_opts = tile_opts;
     if (max_threads <= 0) max_threads = max_threads_for(epb);
-    int nslot = slots_for(a.m, epb, max_threads);
+    a.nslot = slots_for(a.m, epb, max_threads);
     // rows of the SDF legs (nt_contacts.flat) are walked by the environment's slot-lanes too: hundreds per environment in a pile,
     // far more than the tile's own populations ask for -- give them every lane the workgroup may have
-    if (a.ct.flat.row_start) nslot = max_threads / epb;
-    a.nslot = nslot;
-#ifdef NT_ABLATION
-    {
-        static int dbg = -1;
-        if (dbg < 0) { const char* e = getenv("NT_DEBUG_SKIP"); dbg = e ? atoi(e) : 0; }
-        a.debug_skip = dbg;
-    }
-#endif
-    int threads = ((nslot * epb + 63) / 64) * 64;
+    if (a.ct.flat.row_start) a.nslot = max_threads / epb;
     // the pair-heavy tile's wide workgroup (the caller checked the fit): the kernel sizes its per-lane polygon scratch by blockDim.x
-    const int big_lanes = a.m.contact_scratch_in_hbm && threads > NT_BIG_SCENE_LANES ? NT_BIG_SCENE_LANES_WIDE : NT_BIG_SCENE_LANES;
+    const int big_lanes =
+        a.m.contact_scratch_in_hbm && tile_threads(a.nslot, epb) > NT_BIG_SCENE_LANES ? NT_BIG_SCENE_LANES_WIDE : NT_BIG_SCENE_LANES;
     LdsLayout L = make_layout_host(a.m, xpbd_keeps_prestep_state(a.p), uni, tile_opts, big_lanes);
-    size_t lds_bytes = (size_t)(semi ? L.rows_semi : L.rows_per_env) * 4 * epb + (size_t)topo_ints(a.m) * 4 + (size_t)L.uni_floats * 4;
+    const size_t lds_bytes = tile_bytes(semi ? L.rows_semi : L.rows_per_env, epb, topo_ints(a.m), L.uni_floats);
     if (lds_bytes > LDS_BYTES_PER_CU) return NT_ERR_UNSUPPORTED;
-    int blocks = (a.m.env_count + epb - 1) / epb;
-    if (lds_bytes > 48 * 1024) {
-        if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
-            return NT_ERR_LAUNCH;
-    }
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), lds_bytes, stream, a);
-    return hipGetLastError() == hipSuccess ? NT_OK : NT_ERR_LAUNCH;
+    return launch_tile(kernel, a, epb, lds_bytes, stream);
+}
+
+// 4 environments per workgroup run the tile of 8 (collide / XPBD kernels); the convex variants are only instantiated for 1 / 8 / 16
+// (build time): wider tiles run 16
+inline int collide_tile_epb(bool cvx, int epb) { return cvx && epb > 16 ? 16 : epb == 4 ? 8 : epb; }
+
+// -DNT_DEV_FAST (measurement builds of tools/build_variant.py only, never the product): just the headline's kernels -- the analytic
+// XPBD rollout shapes and the 16-environment collide / step kernels -- so that a kernel experiment compiles in a minute instead of six.
+// Everything else answers NT_ERR_UNSUPPORTED.
+#ifdef NT_DEV_FAST
+using TileEpbs = Epbs<16>;
+using TileEpbsCvx = Epbs<>;
+#else
+using TileEpbs = Epbs<64, 32, 16, 8, 1>;
+using TileEpbsCvx = Epbs<16, 8, 1>;
+#endif
+
+// kernels that collide are compiled twice: the convex (MPR/GJK) code only exists in the variant used by models that have convex-routed
+// pairs, so analytic-only models keep their register budget.  f(E, CVX): E environments per workgroup, CVX a std::bool_constant
+template <typename F>
+nt_status dispatch_collide_epb(const nt_model& m, int epb, F&& f) {
+    const bool cvx = m.np_analytic < m.np;
+    epb = collide_tile_epb(cvx, epb);
+    if (cvx) return dispatch_epb(TileEpbsCvx{}, epb, [&](auto E) { return f(E, std::true_type{}); });
+    return dispatch_epb(TileEpbs{}, epb, [&](auto E) { return f(E, std::false_type{}); });
 }
 
 // Launch shape of the analytic (non-convex) fused XPBD rollout: environments per workgroup, workgroup size, minimum waves
@@ -342,35 +360,35 @@ inline bool pick_cvx_uni_shape(const nt_model& m, bool rest, XpbdCfg& c) {
     return false;
 }
 
-// -DNT_DEV_FAST (measurement builds of tools/build_variant.py only, never the product): just the headline's kernels -- the analytic
-// XPBD rollout shapes and the 16-environment collide / step kernels -- so that a kernel experiment compiles in a minute instead of six.
-// Everything else answers NT_ERR_UNSUPPORTED.
-#ifdef NT_DEV_FAST
-#define NT_DISPATCH_EPB(KERNEL, args, epb, stream) ((epb) == 16 ? launch(KERNEL<16>, args, 16, stream) : NT_ERR_UNSUPPORTED)
-#define NT_DISPATCH_EPB_CVX(KERNEL, m, args, epb, stream) \
-    ((m).np_analytic < (m).np || (epb) != 16 ? NT_ERR_UNSUPPORTED : launch(KERNEL<16, false>, args, 16, stream))
-#else
-#define NT_DISPATCH_EPB(KERNEL, args, epb, stream)                                      \
-    ((epb) == 64 ? launch(KERNEL<64>, args, 64, stream)                                 \
-     : (epb) == 32 ? launch(KERNEL<32>, args, 32, stream)                               \
-     : (epb) == 16 ? launch(KERNEL<16>, args, 16, stream)                               \
-     : ((epb) == 8 || (epb) == 4) ? launch(KERNEL<8>, args, 8, stream) : launch(KERNEL<1>, args, 1, stream))
-
-#define NT_DISPATCH_EPB2(KERNEL, B, args, epb, stream)                                  \
-    ((epb) == 64 ? launch(KERNEL<64, B>, args, 64, stream)                              \
-     : (epb) == 32 ? launch(KERNEL<32, B>, args, 32, stream)                            \
-     : (epb) == 16 ? launch(KERNEL<16, B>, args, 16, stream)                            \
-     : ((epb) == 8 || (epb) == 4) ? launch(KERNEL<8, B>, args, 8, stream) : launch(KERNEL<1, B>, args, 1, stream))
-// kernels that collide are compiled twice: the convex (MPR/GJK) code only exists in the variant used by models
-// that have convex-routed pairs, so analytic-only models keep their register budget
-// the convex variants are only instantiated for 1 / 8 / 16 envs per workgroup (build time): wider tiles fall back to 16
-#define NT_DISPATCH_EPB_CVX(KERNEL, m, args, epb, stream)                                              \
-    ((m).np_analytic < (m).np                                                                          \
-         ? ((epb) >= 16 ? launch(KERNEL<16, true>, args, 16, stream)                                   \
-            : ((epb) == 8 || (epb) == 4) ? launch(KERNEL<8, true>, args, 8, stream) : launch(KERNEL<1, true>, args, 1, stream)) \
-         : NT_DISPATCH_EPB2(KERNEL, false, args, epb, stream))
-#endif
-
+// the launch shape of the fused XPBD rollout: nt_xpbd_rollout launches it, nt_xpbd_rollout_shape reports it
+enum class XpbdRoute {
+    none,     // no tile fits the CU
+    refused,  // c: an NT_XPBD_CFG override this model's tile cannot take (reported, never launched)
+    tile,     // c.epb environments per workgroup on the per-environment tiles (pair-heavy models: c.threads lanes)
+    shape,    // c: one of the compiled shapes (launch_xpbd_rollout_shape)
+};
+XpbdRoute plan_xpbd_rollout(const nt_model& m, bool rest, const nt_collide_params* cp, XpbdCfg& c) {
+    const int epb = pick_epb(m, cp ? cp->envs_per_block : 0, rest);
+    if (!epb) return XpbdRoute::none;
+    const bool cvx = m.np_analytic < m.np;
+    if (m.contact_scratch_in_hbm) {
+        c = {1, big_wide_fits(m, rest) ? NT_BIG_SCENE_LANES_WIDE : NT_BIG_SCENE_LANES, 1, 0, 0};
+        return XpbdRoute::tile;
+    }
+    // the tuned shapes: an override for this kind of model, else the uniform-parameter tiles when the parameters allow
+    XpbdCfg o;
+    if (xpbd_cfg_override(o) && (o.cvx != 0) == cvx) {
+        c = o;
+        return (o.uni && (!m.params_uniform || rest)) || !epb_fits(m, o.epb, rest, o.uni != 0) ? XpbdRoute::refused : XpbdRoute::shape;
+    }
+    if (cvx ? (cp == nullptr || cp->envs_per_block == 0) && pick_cvx_uni_shape(m, rest, o) : pick_uni_shape(m, rest, cp, o)) {
+        c = o;
+        return XpbdRoute::shape;
+    }
+    const int e = collide_tile_epb(cvx, epb);
+    c = {e, max_threads_for(e), 1, 0, 0};
+    return XpbdRoute::tile;
+}
 
 }  // namespace
 
@@ -418,7 +436,9 @@ nt_status nt_collide(const nt_model* m, const nt_state* s, nt_contacts* c, const
     a.ct = *c;
     int epb = pick_epb(*m, p ? p->envs_per_block : 0);
     if (!epb) return NT_ERR_UNSUPPORTED;
-    if (m->np == 0) return NT_DISPATCH_EPB(shapes_export_kernel, a, epb, (hipStream_t)stream);  // every pair lives outside the tiles
+    if (m->np == 0)  // every pair lives outside the tiles
+        return dispatch_epb(TileEpbs{}, collide_tile_epb(false, epb),
+                            [&](auto E) { return launch(shapes_export_kernel<E>, a, E, (hipStream_t)stream); });
     // uniform-parameter tile: models whose environments share their parameters stage ONE copy per workgroup instead of 3.8 KB per
     // environment per launch (the per-call API pays the parameter staging in every kernel; the fused rollout once per frame)
     if (m->params_uniform && !m->contact_scratch_in_hbm && m->np_analytic == m->np && epb == 16 && epb_fits(*m, 16, false, true))
@@ -432,7 +452,7 @@ nt_status nt_collide(const nt_model* m, const nt_state* s, nt_contacts* c, const
         return m->np_analytic < m->np ? launch(collide_kernel<1, true, true>, a, 1, (hipStream_t)stream)
                                       : launch(collide_kernel<1, false, true>, a, 1, (hipStream_t)stream);
 #endif
-    return NT_DISPATCH_EPB_CVX(collide_kernel, *m, a, epb, (hipStream_t)stream);
+    return dispatch_collide_epb(*m, epb, [&](auto E, auto CVX) { return launch(collide_kernel<E, CVX>, a, E, (hipStream_t)stream); });
 }
 
 nt_status nt_xpbd_step(const nt_model* m, const nt_xpbd_params* p, nt_state* s_in, nt_state* s_out, const nt_control* ctrl,
@@ -465,7 +485,8 @@ nt_status nt_xpbd_step(const nt_model* m, const nt_xpbd_params* p, nt_state* s_i
 #endif
     if (m->params_uniform && !xpbd_keeps_prestep_state(*p) && epb == 16 && epb_fits(*m, 16, false, true))
         return launch(xpbd_step_kernel<16 + NT_UNI>, a, 16, (hipStream_t)stream, 0, false, true);
-    return NT_DISPATCH_EPB(xpbd_step_kernel, a, epb, (hipStream_t)stream);
+    return dispatch_epb(TileEpbs{}, collide_tile_epb(false, epb),
+                        [&](auto E) { return launch(xpbd_step_kernel<E>, a, E, (hipStream_t)stream); });
 }
 
 nt_status nt_xpbd_rollout(const nt_model* m, const nt_xpbd_params* p, const nt_collide_params* cp, nt_state* s0, nt_state* s1,
@@ -483,63 +504,31 @@ nt_status nt_xpbd_rollout(const nt_model* m, const nt_xpbd_params* p, const nt_c
     a.dt = dt;
     a.substeps = substeps;
     a.tile_opts = NT_TILE_POSE_SNAPSHOT | NT_TILE_LDS_RECORDS;  // (request; launch() grants what the tile has room for)
-    const bool rest = xpbd_keeps_prestep_state(*p);
-    int epb = pick_epb(*m, cp ? cp->envs_per_block : 0, rest);
-    if (!epb) return NT_ERR_UNSUPPORTED;
+    XpbdCfg shape;
+    const XpbdRoute route = plan_xpbd_rollout(*m, xpbd_keeps_prestep_state(*p), cp, shape);
+    if (route == XpbdRoute::none || route == XpbdRoute::refused) return NT_ERR_UNSUPPORTED;
+    if (route == XpbdRoute::shape) return launch_xpbd_rollout_shape(a, shape, (hipStream_t)stream);
 #ifdef NT_DEV_FAST
     if (m->contact_scratch_in_hbm) return NT_ERR_UNSUPPORTED;
 #else
     if (m->contact_scratch_in_hbm) {
         if (a.has_contacts && !a.ct.cw) return NT_ERR_INVALID_ARG;
-        if (big_wide_fits(*m, rest))
+        if (shape.threads == NT_BIG_SCENE_LANES_WIDE)
             return launch(xpbd_rollout_kernel<1, true, true, NT_BIG_SCENE_LANES_WIDE>, a, 1, (hipStream_t)stream, NT_BIG_SCENE_LANES_WIDE);
         return m->np_analytic < m->np ? launch(xpbd_rollout_kernel<1, true, true>, a, 1, (hipStream_t)stream)
                                       : launch(xpbd_rollout_kernel<1, false, true>, a, 1, (hipStream_t)stream);
     }
 #endif
-    if (m->np_analytic < m->np) {  // convex models: uniform-parameter tiles when the parameters allow
-        XpbdCfg c;
-        if (xpbd_cfg_override(c) && c.cvx) {
-            if ((c.uni && (!m->params_uniform || rest)) || !epb_fits(*m, c.epb, rest, c.uni != 0)) return NT_ERR_UNSUPPORTED;
-            return launch_xpbd_rollout_shape(a, c, (hipStream_t)stream);
-        }
-        if ((cp == nullptr || cp->envs_per_block == 0) && pick_cvx_uni_shape(*m, rest, c))
-            return launch_xpbd_rollout_shape(a, c, (hipStream_t)stream);
-    }
-    if (m->np_analytic == m->np) {  // analytic-only models: the tuned launch shapes
-        XpbdCfg c;
-        if (xpbd_cfg_override(c) && !c.cvx) {
-            if ((c.uni && (!m->params_uniform || rest)) || !epb_fits(*m, c.epb, rest, c.uni != 0)) return NT_ERR_UNSUPPORTED;
-            return launch_xpbd_rollout_shape(a, c, (hipStream_t)stream);
-        }
-        if (pick_uni_shape(*m, rest, cp, c)) return launch_xpbd_rollout_shape(a, c, (hipStream_t)stream);
-    }
-    return NT_DISPATCH_EPB_CVX(xpbd_rollout_kernel, *m, a, epb, (hipStream_t)stream);
+    return dispatch_collide_epb(*m, shape.epb,
+                                [&](auto E, auto CVX) { return launch(xpbd_rollout_kernel<E, CVX>, a, E, (hipStream_t)stream); });
 }
 
 nt_status nt_xpbd_rollout_shape(const nt_model* m, const nt_xpbd_params* p, const nt_collide_params* cp, int32_t out[5]) {
     if (!model_ok(m) || !p || !out) return NT_ERR_INVALID_ARG;
-    const bool rest = xpbd_keeps_prestep_state(*p);
-    int epb = pick_epb(*m, cp ? cp->envs_per_block : 0, rest);
-    if (!epb) return NT_ERR_UNSUPPORTED;
-    const bool cvx = m->np_analytic < m->np, big = m->contact_scratch_in_hbm != 0;
-    XpbdCfg c = {epb, max_threads_for(epb), 1, 0, 0};
-    if (big) c = {1, big_wide_fits(*m, rest) ? NT_BIG_SCENE_LANES_WIDE : NT_BIG_SCENE_LANES, 1, 0, 0};
-    else if (!cvx) {
-        XpbdCfg o;
-        if (xpbd_cfg_override(o) && !o.cvx) c = o;
-        else if (pick_uni_shape(*m, rest, cp, o)) c = o;
-        else if (epb == 4) c.epb = 8;
-    } else {
-        XpbdCfg o;
-        if (xpbd_cfg_override(o) && o.cvx) c = o;
-        else if ((cp == nullptr || cp->envs_per_block == 0) && pick_cvx_uni_shape(*m, rest, o)) c = o;
-        else {
-            c.epb = epb >= 16 ? 16 : (epb >= 4 ? 8 : 1);
-            c.threads = max_threads_for(c.epb);
-        }
-    }
-    out[0] = c.epb; out[1] = c.threads; out[2] = c.minw; out[3] = c.uni; out[4] = (cvx ? 1 : 0) | (big ? 2 : 0);
+    XpbdCfg c;
+    if (plan_xpbd_rollout(*m, xpbd_keeps_prestep_state(*p), cp, c) == XpbdRoute::none) return NT_ERR_UNSUPPORTED;
+    out[0] = c.epb; out[1] = c.threads; out[2] = c.minw; out[3] = c.uni;
+    out[4] = (m->np_analytic < m->np ? 1 : 0) | (m->contact_scratch_in_hbm ? 2 : 0);
     return NT_OK;
 }
 
@@ -562,16 +551,9 @@ nt_status nt_semi_implicit_step(const nt_model* m, const nt_semi_implicit_params
 #else
     int epb = pick_epb(*m, envs_per_block);
     if (!epb) return NT_ERR_UNSUPPORTED;
-    if ((size_t)make_layout_host(*m).rows_semi * 4 * epb + (size_t)topo_ints(*m) * 4 > LDS_BYTES_PER_CU) {
-        // the wrench records of SolverSemiImplicit make its tile heavier than the collide / XPBD one: narrow it
-        while (epb > 8 && (size_t)make_layout_host(*m).rows_semi * 4 * epb + (size_t)topo_ints(*m) * 4 > LDS_BYTES_PER_CU) epb /= 2;
-        if ((size_t)make_layout_host(*m).rows_semi * 4 * epb + (size_t)topo_ints(*m) * 4 > LDS_BYTES_PER_CU) epb = 1;
-    }
-    return epb == 64 ? launch(semi_implicit_step_kernel<64>, a, 64, (hipStream_t)stream, 0, true)
-         : epb == 32 ? launch(semi_implicit_step_kernel<32>, a, 32, (hipStream_t)stream, 0, true)
-         : epb == 16 ? launch(semi_implicit_step_kernel<16>, a, 16, (hipStream_t)stream, 0, true)
-         : epb == 8 ? launch(semi_implicit_step_kernel<8>, a, 8, (hipStream_t)stream, 0, true)
-                    : launch(semi_implicit_step_kernel<1>, a, 1, (hipStream_t)stream, 0, true);
+    epb = narrow_semi_epb(*m, epb, make_layout_host(*m).rows_semi);
+    return dispatch_epb(Epbs<64, 32, 16, 8, 1>{}, epb == 4 ? 1 : epb,  // (4 environments per workgroup run the tile of 1)
+                        [&](auto E) { return launch(semi_implicit_step_kernel<E>, a, E, (hipStream_t)stream, 0, true); });
 #endif
 }
 
@@ -597,33 +579,17 @@ nt_status nt_semi_implicit_rollout(const nt_model* m, const nt_semi_implicit_par
 #else
     int epb = pick_epb(*m, cp ? cp->envs_per_block : 0);
     if (!epb) return NT_ERR_UNSUPPORTED;
-    const bool cvx = m->np_analytic < m->np;
-    if (epb == 4) epb = 8;
-    if (cvx && epb > 16) epb = 16;  // the convex variants are only instantiated for 1 / 8 / 16 envs per workgroup (build time)
     // host twin of the kernel's tile (place_semi_rollout): wrench records or collide scratch, whichever is larger, behind the
-    // persistent block -- heavier than the collide / XPBD tile when the records dominate: narrow it like nt_semi_implicit_step does
+    // persistent block
     LdsLayout L = make_layout(*m, false, false, false, false);
-    const size_t row_bytes = (size_t)place_semi_rollout(L, *m) * 4, shared_bytes = (size_t)topo_ints(*m) * 4;
-    while (epb > 8 && row_bytes * epb + shared_bytes > LDS_BYTES_PER_CU) epb /= 2;
-    if (row_bytes * epb + shared_bytes > LDS_BYTES_PER_CU) epb = 1;
-    const size_t lds_bytes = row_bytes * epb + shared_bytes;
+    const int rows = place_semi_rollout(L, *m);
+    epb = narrow_semi_epb(*m, collide_tile_epb(m->np_analytic < m->np, epb), rows);
+    const size_t lds_bytes = tile_bytes(rows, epb, topo_ints(*m));
     if (lds_bytes > LDS_BYTES_PER_CU) return NT_ERR_UNSUPPORTED;
     a.nslot = slots_for(*m, epb, max_threads_for(epb));
-    const int threads = ((a.nslot * epb + 63) / 64) * 64, blocks = (m->env_count + epb - 1) / epb;
-    auto go = [&](auto kernel) -> nt_status {
-        if (lds_bytes > 48 * 1024 &&
-            hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
-            return NT_ERR_LAUNCH;
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), lds_bytes, (hipStream_t)stream, a);
-        return hipGetLastError() == hipSuccess ? NT_OK : NT_ERR_LAUNCH;
-    };
-    if (cvx)
-        return epb == 16 ? go(semi_implicit_rollout_kernel<16, true>)
-             : epb == 8 ? go(semi_implicit_rollout_kernel<8, true>) : go(semi_implicit_rollout_kernel<1, true>);
-    return epb == 64 ? go(semi_implicit_rollout_kernel<64, false>)
-         : epb == 32 ? go(semi_implicit_rollout_kernel<32, false>)
-         : epb == 16 ? go(semi_implicit_rollout_kernel<16, false>)
-         : epb == 8 ? go(semi_implicit_rollout_kernel<8, false>) : go(semi_implicit_rollout_kernel<1, false>);
+    return dispatch_collide_epb(*m, epb, [&](auto E, auto CVX) {
+        return launch_tile(semi_implicit_rollout_kernel<E, CVX>, a, E, lds_bytes, (hipStream_t)stream);
+    });
 #endif
 }
 

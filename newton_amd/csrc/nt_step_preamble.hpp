@@ -83,4 +83,50 @@ bool model_ok(const nt_model* m) {
            (m->np_analytic == m->np || m->cpp == 5);
 }
 
+// ------------------------------------------------------------------------------------------------
+// tile launch (every stepping kernel: one workgroup owns `epb` environments, KArgs::nslot slot-lanes each)
+// ------------------------------------------------------------------------------------------------
+// LDS bytes of a tile: `rows` floats per environment (LdsLayout / FsLayout rows), then the block-shared ints (topology) and floats
+// (the one parameter copy of a uniform-parameter tile)
+inline size_t tile_bytes(int rows, int epb, size_t shared_ints, int uni_floats = 0) {
+    return (size_t)rows * 4 * epb + shared_ints * 4 + (size_t)uni_floats * 4;
+}
+
+// workgroup size: the slot-lanes of `epb` environments, in whole waves
+inline int tile_threads(int nslot, int epb) { return ((nslot * epb + 63) / 64) * 64; }
+
+// the phase-ablation mask of measurement builds (-DNT_ABLATION), read once per process
+#ifdef NT_ABLATION
+inline int debug_skip() {
+    static int dbg = -1;
+    if (dbg < 0) { const char* e = getenv("NT_DEBUG_SKIP"); dbg = e ? atoi(e) : 0; }
+    return dbg;
+}
+#endif
+
+// one workgroup per `epb` environments, a.nslot slot-lanes each, `lds_bytes` of dynamic LDS (opted in above the 48 KB default);
+// `extra`: the kernel's arguments behind KArgs
+template <typename K, typename... A>
+nt_status launch_tile(K kernel, KArgs a, int epb, size_t lds_bytes, hipStream_t stream, A... extra) {
+#ifdef NT_ABLATION
+    a.debug_skip = debug_skip();
+#endif
+    if (lds_bytes > 48 * 1024 &&
+        hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
+        return NT_ERR_LAUNCH;
+    hipLaunchKernelGGL(kernel, dim3((a.m.env_count + epb - 1) / epb), dim3(tile_threads(a.nslot, epb)), lds_bytes, stream, a, extra...);
+    return hipGetLastError() == hipSuccess ? NT_OK : NT_ERR_LAUNCH;
+}
+
+// runtime environments per workgroup -> compiled instantiation: f(std::integral_constant<int, E>) for the E of the list equal to
+// `epb`; NT_ERR_UNSUPPORTED when none is (each call site maps its runtime values onto its list first)
+template <int... Es>
+struct Epbs {};
+template <int... Es, typename F>
+nt_status dispatch_epb(Epbs<Es...>, int epb, F&& f) {
+    nt_status r = NT_ERR_UNSUPPORTED;
+    (void)((epb == Es && ((r = f(std::integral_constant<int, Es>{})), true)) || ...);
+    return r;
+}
+
 }  // namespace

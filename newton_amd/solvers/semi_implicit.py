@@ -34,10 +34,7 @@ class SolverSemiImplicit(SolverBase):
 
     def step(self, state_in, state_out, control, contacts, dt: float) -> None:
         dm = self.dm
-        if control is None:
-            if not hasattr(self, "_control"):
-                self._control = self.model.control()
-            control = self._control
+        control = self._control_or_default(control)
         p = self._params()
         d_in, d_out, d_c = state_in._desc(), state_out._desc(), control._desc()
         d_in = self._state_desc_with_sdf_forces(state_in, contacts, self.friction_smoothing)
@@ -49,31 +46,8 @@ class SolverSemiImplicit(SolverBase):
     def rollout(self, state_0, state_1, control, contacts, dt: float, substeps: int):
         """substeps x {clear_forces; collide; step; swap} in ONE launch (``nt_semi_implicit_rollout``); returns the state
         object holding the result (state_0 for an even number of substeps, state_1 for odd -- the reference loop's swap)."""
-        dm = self.dm
-        if control is None:
-            if not hasattr(self, "_control"):
-                self._control = self.model.control()
-            control = self._control
-        leg = getattr(contacts, "_sdf_leg", None)
-        if leg is not None:
-            # the SDF legs of collide() are a chain of launches of their own (newton_amd/sdf_pipeline.py): run the reference loop
-            # launch by launch, like the other solvers' rollouts do for such models (step adds the rows' penalty wrenches)
-            cp = _lib.nt_collide_params(0, self.envs_per_block)
-            for _ in range(int(substeps)):
-                state_0.clear_forces()
-                d_s, d_ct = state_0._desc(), contacts._desc()
-                leg.export_pointers(d_ct)
-                _lib.check(dm.lib.nt_collide(C.byref(dm.desc), C.byref(d_s), C.byref(d_ct), C.byref(cp), dm.stream()), "nt_collide")
-                leg.collide(state_0, contacts._flat, dm.stream())
-                contacts._generation += 1
-                self.step(state_0, state_1, control, contacts, dt)
-                state_0, state_1 = state_1, state_0
-            return state_0
-        p = self._params()
+        control = self._control_or_default(control)
         cp = _lib.nt_collide_params(0, self.envs_per_block)
-        d0, d1, d_c, d_ct = state_0._desc(), state_1._desc(), control._desc(), contacts._desc()
-        _lib.check(dm.lib.nt_semi_implicit_rollout(C.byref(dm.desc), C.byref(p), C.byref(cp), C.byref(d0), C.byref(d1),
-                                                   C.byref(d_c), C.byref(d_ct), float(dt), int(substeps), dm.stream()),
-                   "nt_semi_implicit_rollout")
-        contacts._generation += 1
-        return state_1 if substeps % 2 else state_0
+        if getattr(contacts, "_sdf_leg", None) is not None:  # (step adds the penalty wrenches of the SDF legs' rows)
+            return self._rollout_by_launch(state_0, state_1, control, contacts, dt, substeps, cp)
+        return self._rollout_fused("nt_semi_implicit_rollout", self._params(), cp, state_0, state_1, control, contacts, dt, substeps)

@@ -49,8 +49,7 @@ class SolverXPBD(SolverBase):
 
     def step(self, state_in, state_out, control, contacts, dt: float) -> None:
         dm = self.dm
-        if control is None:
-            control = self._default_control()
+        control = self._control_or_default(control)
         p = self._params()
         d_in, d_out, d_c = state_in._desc(), state_out._desc(), control._desc()
         if contacts is not None and getattr(contacts, "_flat", None) is not None and self.enable_restitution:
@@ -115,36 +114,13 @@ class SolverXPBD(SolverBase):
     def rollout(self, state_0, state_1, control, contacts, dt: float, substeps: int, collide_params=None):
         """substeps x {clear_forces; collide; step; swap} in one launch.  Returns the state object holding the
         result (state_0 for an even number of substeps, state_1 for odd -- the reference loop's swap)."""
-        dm = self.dm
-        if control is None:
-            control = self._default_control()
+        control = self._control_or_default(control)
         cp = collide_params if collide_params is not None else _lib.nt_collide_params(0, self.envs_per_block)
-        leg = getattr(contacts, "_sdf_leg", None)
-        if contacts.force is not None or state_0._parent_f is not None or state_1._parent_f is not None or leg is not None:
+        if (contacts.force is not None or state_0._parent_f is not None or state_1._parent_f is not None or
+                getattr(contacts, "_sdf_leg", None) is not None):
             # the reporting outputs only exist in the per-substep kernel, and the SDF leg of collide() is a chain of launches
             # of its own: run the reference loop launch by launch
-            for _ in range(int(substeps)):
-                state_0.clear_forces()
-                d_s, d_ct = state_0._desc(), contacts._desc()
-                if leg is not None:
-                    leg.export_pointers(d_ct)
-                _lib.check(dm.lib.nt_collide(C.byref(dm.desc), C.byref(d_s), C.byref(d_ct), C.byref(cp), dm.stream()),
-                           "nt_collide")
-                if leg is not None:
-                    leg.collide(state_0, contacts._flat, dm.stream())
-                contacts._generation += 1
-                self.step(state_0, state_1, control, contacts, dt)
-                state_0, state_1 = state_1, state_0
-            return state_0
+            return self._rollout_by_launch(state_0, state_1, control, contacts, dt, substeps, cp)
         p = self._params()
         contacts.prepare_rollout()  # (pair-heavy scenes: the rollout's own contact records, allocated on first use)
-        d0, d1, d_c, d_ct = state_0._desc(), state_1._desc(), control._desc(), contacts._desc()
-        _lib.check(dm.lib.nt_xpbd_rollout(C.byref(dm.desc), C.byref(p), C.byref(cp), C.byref(d0), C.byref(d1), C.byref(d_c),
-                                          C.byref(d_ct), float(dt), int(substeps), dm.stream()), "nt_xpbd_rollout")
-        contacts._generation += 1
-        return state_1 if substeps % 2 else state_0
-
-    def _default_control(self):
-        if not hasattr(self, "_control"):
-            self._control = self.model.control()
-        return self._control
+        return self._rollout_fused("nt_xpbd_rollout", p, cp, state_0, state_1, control, contacts, dt, substeps)
