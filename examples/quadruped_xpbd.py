@@ -46,6 +46,10 @@ def main():
     q, qd = state_0.body_q, state_0.body_qd
     root_z = q.reshape(args.worlds, -1, 7)[:, 0, 2]
     print(f"root height {float(root_z.mean()):.3f} m (expected 0.46 +/- 0.01), max |qd| {float(qd.abs().max()):.3f}")
+    # what an RL loop observes: SolverXPBD advances the bodies only, eval_ik brings state.joint_q / joint_qd up to date
+    newton.eval_ik(model, state_0)
+    dof_q = newton.selection.ArticulationView(model, "*").get_dof_positions(state_0)
+    print(f"dof positions after the last frame: leg joints within [{float(dof_q[:, 7:].min()):.3f}, {float(dof_q[:, 7:].max()):.3f}] rad")
 
 
 if __name__ == "__main__":

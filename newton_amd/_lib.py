@@ -430,6 +430,9 @@ SYMBOLS = {
                                                     C.POINTER(nt_contact_report), _P]),
     "nt_contacts_order_save_groups": (C.c_int32, [C.c_int32, C.POINTER(nt_contact_group), C.POINTER(nt_sorted_contacts),
                                                   C.POINTER(nt_contact_report), _P]),
+    # include/newton_hip_kinematics.h
+    "nt_eval_ik": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_state), _P, _P, _P, _P]),
+    "nt_eval_ik_tile": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_state), _P, _P, _P, C.c_int32, _P]),
     "nt_hydro_collide": (C.c_int32, [C.POINTER(nt_hydro_args), _P]),
     "nt_hydro_pairs": (C.c_int32, [C.POINTER(nt_hydro_args), _P]),
     "nt_sdf_candidate_pairs": (C.c_int32, [C.POINTER(nt_sdf_scene), _P, _P, _P, _P, _P, _P]),

@@ -1,7 +1,8 @@
-"""eval_fk: joint coordinates -> maximal coordinates (newton/_src/sim/articulation.py:236-573).
+"""eval_fk: joint coordinates -> maximal coordinates (newton/_src/sim/articulation.py:236-573), and eval_ik, its inverse.
 
-Host implementation (numpy, vectorised over environments) used to seed ``body_q`` / ``body_qd`` before stepping;
-it is model-preparation code, not part of the per-substep hot path.
+Host implementations (numpy, vectorised over environments): eval_fk_numpy seeds ``body_q`` / ``body_qd`` before stepping, it is
+model-preparation code, not part of the per-substep hot path; eval_ik_numpy is the host mirror of the device kernel behind
+``eval_ik`` (nt_eval_ik, include/newton_hip_kinematics.h) and serves host models only.
 """
 from __future__ import annotations
 
@@ -185,20 +186,26 @@ def _host_array(x):
     return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
 
 
-def _fk_body_selection(model, mask, indices, body_flag_filter):
-    """bool [body_count]: bodies whose inbound joint belongs to a selected articulation and whose flags pass the filter."""
+def _articulation_selection(model, mask, indices, what):
+    """bool [articulation_count] from ``mask`` (bool per articulation) or ``indices`` (articulation ids); all when neither is given."""
     A = int(model.articulation_count)
     if mask is not None and indices is not None:
-        raise ValueError("eval_fk: 'mask' and 'indices' cannot be used together")
+        raise ValueError(f"{what}: 'mask' and 'indices' cannot be used together")
     art_sel = np.ones(A, dtype=bool)
     if mask is not None:
         art_sel = np.asarray(mask.detach().cpu().numpy() if hasattr(mask, "detach") else mask).astype(bool).reshape(-1)
         if art_sel.shape[0] != A:
-            raise ValueError(f"eval_fk: mask has {art_sel.shape[0]} entries, the model has {A} articulations")
+            raise ValueError(f"{what}: mask has {art_sel.shape[0]} entries, the model has {A} articulations")
     if indices is not None:
         idx = np.asarray(indices.detach().cpu().numpy() if hasattr(indices, "detach") else indices, dtype=np.int64).reshape(-1)
         art_sel = np.zeros(A, dtype=bool)
         art_sel[idx] = True
+    return art_sel
+
+
+def _fk_body_selection(model, mask, indices, body_flag_filter):
+    """bool [body_count]: bodies whose inbound joint belongs to a selected articulation and whose flags pass the filter."""
+    art_sel = _articulation_selection(model, mask, indices, "eval_fk")
     joint_art = np.asarray(model.joint_articulation)
     sel = np.zeros(model.body_count, dtype=bool)
     ok = joint_art >= 0
@@ -262,3 +269,273 @@ def eval_fk(model, joint_q, joint_qd, state, mask=None, indices=None, body_flag_
     bq, bqd = eval_fk_numpy(model, host(joint_q), host(joint_qd))
     state.body_q = bq
     state.body_qd = bqd
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# eval_ik
+# ---------------------------------------------------------------------------------------------------------------------------------
+_D6_ORTHOGONAL_TOL = 1e-4
+
+
+def check_ik_supported(model):
+    """eval_ik recovers the angles of a D6 joint with two or three angular axes as Euler angles in the frame of those axes: they must be
+    mutually orthogonal.  Raises NotImplementedError (the C ABI's NT_ERR_UNSUPPORTED) otherwise; checked once per model."""
+    if getattr(model, "_ik_checked", False):
+        return
+    jt = np.asarray(model.joint_type)
+    dd = np.asarray(model.joint_dof_dim).reshape(-1, 2)
+    axis = np.asarray(model.joint_axis, dtype=np.float64).reshape(-1, 3)
+    qds = np.asarray(model.joint_qd_start)
+    for j in np.flatnonzero((jt == int(JointType.D6)) & (dd[:, 1] >= 2)):
+        a = axis[qds[j] + dd[j, 0]:qds[j] + dd[j, 0] + dd[j, 1]]
+        g = a @ a.T
+        if np.abs(g - np.diag(np.diag(g))).max() > _D6_ORTHOGONAL_TOL:
+            raise NotImplementedError(f"eval_ik: joint {j} is a D6 joint with {dd[j, 1]} angular axes that are not mutually orthogonal "
+                                      "(unsupported)")
+    model._ik_checked = True
+
+
+def _wrap_pi(a):
+    a = np.where(a > np.pi, a - 2.0 * np.pi, a)
+    return np.where(a <= -np.pi, a + 2.0 * np.pi, a)
+
+
+def _twist_angle(axis, q):
+    return _wrap_pi(2.0 * np.arctan2(np.sum(axis * q[..., :3], axis=-1), q[..., 3]))
+
+
+def _d6_angles(ang, e, q_j):
+    """Intrinsic Euler angles of q_j in the frame whose columns are the axes e[0..ang-1] (mutually orthogonal)."""
+    e2 = e[2] if ang == 3 else np.cross(e[0], e[1])
+    r0, r1, r2 = _qrot(q_j, e[0]), _qrot(q_j, e[1]), _qrot(q_j, e2)
+
+    def d(a, b):
+        return np.sum(a * b, axis=-1)
+
+    if ang == 2:
+        return [np.arctan2(d(e2, r1), d(e[1], r1)), np.arctan2(d(e[0], r2), d(e[0], r0))]
+    s = np.where(d(np.cross(e[0], e[1]), e2) < 0.0, -1.0, 1.0)
+    m00, m01, m02 = d(e[0], r0), d(e[0], r1), d(e[0], r2)
+    return [s * np.arctan2(-d(e[1], r2), d(e2, r2)), s * np.arctan2(m02, np.sqrt(m00 * m00 + m01 * m01)), s * np.arctan2(-m01, m00)]
+
+
+def eval_ik_numpy(model, body_q, body_qd, joint_q=None, joint_qd=None, art_sel=None):
+    """Host mirror of eval_ik_kernel: returns (joint_q, joint_qd) as float32 arrays in Newton's flat order.  ``joint_q`` / ``joint_qd``
+    (default: the model's) supply the entries that stay untouched: FIXED joints have none, and with ``art_sel`` (bool per articulation)
+    the joints of unselected articulations and joints outside any articulation keep theirs."""
+    if getattr(model, "is_heterogeneous", False):  # per world group, world-major concatenation (hetero.py)
+        parts = model.world_groups.parts
+        cut = lambda a, key: np.split(np.asarray(a, dtype=np.float32), np.cumsum([getattr(p, key) for p in parts])[:-1])  # noqa: E731
+        bq, bqd = cut(np.asarray(body_q).reshape(-1, 7), "body_count"), cut(np.asarray(body_qd).reshape(-1, 6), "body_count")
+        jq = cut(model.joint_q if joint_q is None else joint_q, "joint_coord_count")
+        jqd = cut(model.joint_qd if joint_qd is None else joint_qd, "joint_dof_count")
+        sel = [None] * len(parts) if art_sel is None else np.split(np.asarray(art_sel, dtype=bool),
+                                                                  np.cumsum([p.articulation_count for p in parts])[:-1])
+        res = [eval_ik_numpy(p, *args) for p, *args in zip(parts, bq, bqd, jq, jqd, sel)]
+        return np.concatenate([r[0] for r in res]), np.concatenate([r[1] for r in res])
+    check_ik_supported(model)
+    t = model.env
+    E, nb, nj = t.env_count, t.nb, t.nj
+    bq = np.asarray(body_q, dtype=np.float64).reshape(E, nb, 7)
+    bqd = np.asarray(body_qd, dtype=np.float64).reshape(E, nb, 6)
+    out_q = np.array(model.joint_q if joint_q is None else joint_q, dtype=np.float32).reshape(E, t.nc)
+    out_qd = np.array(model.joint_qd if joint_qd is None else joint_qd, dtype=np.float32).reshape(E, t.nd)
+    com = np.asarray(model.body_com, dtype=np.float64).reshape(E, nb, 3)
+    X_p = np.asarray(model.joint_X_p, dtype=np.float64).reshape(E, nj, 7)
+    X_c = np.asarray(model.joint_X_c, dtype=np.float64).reshape(E, nj, 7)
+    axis_all = np.asarray(model.joint_axis, dtype=np.float64).reshape(E, t.nd, 3)
+    art = np.asarray(model.joint_articulation).reshape(E, nj) if nj else np.zeros((E, 0), dtype=np.int64)
+    handled = (JointType.PRISMATIC, JointType.REVOLUTE, JointType.BALL, JointType.FREE, JointType.DISTANCE, JointType.D6)
+    for j in range(nj):
+        jt = int(t.joint_type[j])
+        if jt not in [int(h) for h in handled]:
+            continue
+        rows = np.ones(E, dtype=bool)
+        if art_sel is not None:
+            rows = (art[:, j] >= 0) & np.asarray(art_sel, dtype=bool)[np.maximum(art[:, j], 0)]
+            if not rows.any():
+                continue
+        parent, child = int(t.joint_parent[j]), int(t.joint_child[j])
+        qs, qds = int(t.joint_q_start[j]), int(t.joint_qd_start[j])
+        lin, ang = int(t.joint_lin_count[j]), int(t.joint_ang_count[j])
+        X_wpj = X_p[:, j]
+        if parent >= 0:
+            X_wp = bq[:, parent]
+            X_wpj = _xmul(X_wp, X_wpj)
+        X_wc = bq[:, child]
+        X_wcj = _xmul(X_wc, X_c[:, j])
+        q_pinv = _qinv(X_wpj[:, 3:])
+        x_j = _qrot(q_pinv, X_wcj[:, :3] - X_wpj[:, :3])
+        q_j = _qmul(q_pinv, X_wcj[:, 3:])
+        w_o = bqd[:, child, 3:]
+        com_w = _qrot(X_wc[:, 3:], com[:, child])
+        v_o = bqd[:, child, :3] - np.cross(w_o, com_w)
+        w_parent = np.zeros((E, 3))
+        v_parent = np.zeros((E, 3))
+        if parent >= 0:
+            w_parent = bqd[:, parent, 3:]
+            v_parent = np.cross(w_parent, X_wc[:, :3] - (X_wp[:, :3] + _qrot(X_wp[:, 3:], com[:, parent]))) + bqd[:, parent, :3]
+        ang_w, lin_origin = w_o - w_parent, v_o - v_parent
+        if jt in (JointType.FREE, JointType.DISTANCE):
+            lin_w = lin_origin + np.cross(ang_w, com_w)
+        else:
+            lin_w = lin_origin - np.cross(ang_w, X_wc[:, :3] - X_wcj[:, :3])
+        v_lin, v_ang = _qrot(q_pinv, lin_w), _qrot(q_pinv, ang_w)
+
+        def dot(a, b):
+            return np.sum(a * b, axis=-1)
+
+        q_new, qd_new = [], []
+        if jt == JointType.PRISMATIC:
+            q_new, qd_new = [dot(axis_all[:, qds], x_j)], [dot(axis_all[:, qds], v_lin)]
+        elif jt == JointType.REVOLUTE:
+            q_new, qd_new = [_twist_angle(axis_all[:, qds], q_j)], [dot(axis_all[:, qds], v_ang)]
+        elif jt == JointType.BALL:
+            q_new, qd_new = list(q_j.T), list(v_ang.T)
+        elif jt in (JointType.FREE, JointType.DISTANCE):
+            q_new, qd_new = list(x_j.T) + list(q_j.T), list(v_lin.T) + list(v_ang.T)
+        else:  # D6
+            for k in range(lin):
+                q_new.append(dot(axis_all[:, qds + k], x_j))
+                qd_new.append(dot(axis_all[:, qds + k], v_lin))
+            e = [axis_all[:, qds + lin + k] for k in range(ang)]
+            if ang == 1:
+                q_new.append(_twist_angle(e[0], q_j))
+                qd_new.append(dot(e[0], v_ang))
+            elif ang >= 2:
+                th = _d6_angles(ang, e, q_j)
+                # eval_fk's transported axes at the recovered angles; v_ang = sum a_k qd_k (Cramer)
+                a0 = e[0]
+                a1 = _qrot(_quat_axis_angle(a0, th[0]), e[1])
+                q_new += th
+                if ang == 2:
+                    g00, g01, g11, b0, b1 = dot(a0, a0), dot(a0, a1), dot(a1, a1), dot(a0, v_ang), dot(a1, v_ang)
+                    det = g00 * g11 - g01 * g01
+                    qd_new += [(b0 * g11 - b1 * g01) / det, (g00 * b1 - g01 * b0) / det]
+                else:
+                    q_10 = _qmul(_quat_axis_angle(a1, th[1]), _quat_axis_angle(a0, th[0]))
+                    a2 = _qrot(q_10, e[2])
+                    a12 = np.cross(a1, a2)
+                    det = dot(a0, a12)
+                    qd_new += [dot(v_ang, a12) / det, dot(a0, np.cross(v_ang, a2)) / det, dot(a0, np.cross(a1, v_ang)) / det]
+        for k, v in enumerate(q_new):
+            out_q[rows, qs + k] = v[rows]
+        for k, v in enumerate(qd_new):
+            out_qd[rows, qds + k] = v[rows]
+    return out_q.reshape(-1), out_qd.reshape(-1)
+
+
+def _fill(dst, values):
+    """Write ``values`` (flat, Newton order) into the caller's tensor / array in place."""
+    if hasattr(dst, "copy_"):
+        dst.copy_(values.reshape(dst.shape) if hasattr(values, "device") else dst.new_tensor(np.asarray(values)).reshape(dst.shape))
+    else:
+        dst[...] = (values.detach().cpu().numpy() if hasattr(values, "detach") else np.asarray(values)).reshape(dst.shape)
+
+
+def _eval_ik_device(model, state, joint_q, joint_qd, art_mask):
+    """One launch of eval_ik_kernel on the model's stream.  art_mask: uint8 device tensor [env_count * na] or None."""
+    import ctypes as C  # noqa: PLC0415
+
+    from . import _lib  # noqa: PLC0415
+    from .state import pack_soa  # noqa: PLC0415
+
+    t = model.env
+    dm = model.device_model()
+    d = state._desc()
+    # the state's own SoA buffers (no copy), or SoA twins of the caller's arrays (they supply the entries that stay untouched)
+    soa_q = state._soa["joint_q"] if joint_q is None else pack_soa(model, joint_q, 1, t.nc)
+    soa_qd = state._soa["joint_qd"] if joint_qd is None else pack_soa(model, joint_qd, 1, t.nd)
+    _lib.check(dm.lib.nt_eval_ik(C.byref(dm.desc), C.byref(d), soa_q.data_ptr(), soa_qd.data_ptr(),
+                                 None if art_mask is None else art_mask.data_ptr(), dm.stream()), "nt_eval_ik")
+    for dst, soa, n in ((joint_q, soa_q, t.nc), (joint_qd, soa_qd, t.nd)):
+        if dst is None or n == 0:
+            continue
+        import torch  # noqa: PLC0415
+
+        flat = torch.empty(t.env_count * n, dtype=torch.float32, device=dm.device)
+        _lib.check(dm.lib.nt_unpack_aos(soa.data_ptr(), flat.data_ptr(), 1, n, t.env_count, t.env_stride, dm.stream()), "nt_unpack_aos")
+        _fill(dst, flat)
+
+
+def eval_ik(model, state, joint_q=None, joint_qd=None, mask=None, indices=None):
+    """newton.eval_ik(model, state, joint_q, joint_qd, mask=None, indices=None) (newton/_src/sim/articulation.py): joint coordinates and
+    velocities from ``state.body_q`` / ``state.body_qd`` -- the inverse of :func:`eval_fk`.  The maximal-coordinate solvers (SolverXPBD,
+    SolverSemiImplicit) never touch ``state.joint_q`` / ``state.joint_qd``: step, call ``eval_ik``, then read them (or an
+    ``ArticulationView``).
+
+    With ``joint_q`` / ``joint_qd`` left ``None`` the state's own arrays are written in place: on a GPU model, without ``mask`` /
+    ``indices``, that is one kernel launch on the model's stream, no copy, no allocation, no synchronisation -- it records into
+    ``newton_amd.graph.capture``.  Only that path is: a selection uploads its byte mask on every call (one allocation and one
+    host-to-device copy; ``nt_eval_ik`` itself takes a resident mask and stays capturable), given tensors / arrays are filled in
+    Newton's flat order through staging buffers.  Every joint of the model is evaluated, inside an articulation or not; ``mask`` (bool per articulation) or
+    ``indices`` (articulation ids) restrict the update: the joints of unselected articulations and joints outside any articulation
+    are left untouched.  FIXED joints have no coordinates.  A D6 joint with two or three angular axes needs them mutually orthogonal
+    (the angles are Euler angles in the frame of the axes); any other is refused as unsupported (NotImplementedError).  Joints that the
+    solver left slightly violated are projected onto their coordinates."""
+    art_sel = None
+    if mask is not None or indices is not None:
+        art_sel = _articulation_selection(model, mask, indices, "eval_ik")
+        if art_sel.all() and not np.any(np.asarray(model.joint_articulation) == -1):
+            art_sel = None
+    if getattr(model, "is_heterogeneous", False):
+        return _eval_ik_groups(model, state, joint_q, joint_qd, art_sel)
+    check_ik_supported(model)
+    t = model.env
+    if getattr(model, "is_gpu", False):
+        from .state import State  # noqa: PLC0415
+
+        if not isinstance(state, State):
+            raise TypeError("eval_ik: a GPU model needs a State (the body state is read on the device)")
+        if t.nj == 0:
+            return
+        art_mask = None
+        if art_sel is not None:
+            if t.na == 0 or t.na * t.env_count != art_sel.shape[0]:
+                raise NotImplementedError("eval_ik: mask / indices need articulations that cover every world's joints in order")
+            import torch  # noqa: PLC0415
+
+            art_mask = torch.from_numpy(art_sel.astype(np.uint8)).to(model.device_model().device)
+        _eval_ik_device(model, state, joint_q, joint_qd, art_mask)
+        return
+    jq, jqd = eval_ik_numpy(model, _host_array(state.body_q), _host_array(state.body_qd),
+                            _host_array(state.joint_q if joint_q is None else joint_q),
+                            _host_array(state.joint_qd if joint_qd is None else joint_qd), art_sel)
+    if joint_q is None:
+        state.joint_q = jq
+    else:
+        _fill(joint_q, jq)
+    if joint_qd is None:
+        state.joint_qd = jqd
+    else:
+        _fill(joint_qd, jqd)
+
+
+def _eval_ik_groups(model, state, joint_q, joint_qd, art_sel):
+    """Heterogeneous model: one eval_ik per world group into the parts of the GroupedState, the groups on their sibling streams."""
+    groups = model.world_groups
+    parts = groups.parts
+
+    def cut(value, key):
+        if value is None:
+            return [None] * len(parts)
+        sizes = [getattr(p, key) for p in parts]
+        if hasattr(value, "split") and hasattr(value, "device"):
+            return list(value.reshape(-1).split(sizes))
+        return np.split(np.asarray(value).reshape(-1), np.cumsum(sizes)[:-1])  # (views: filled in place)
+
+    if joint_q is not None and not hasattr(joint_q, "device") and not isinstance(joint_q, np.ndarray):
+        raise TypeError("eval_ik: joint_q must be a tensor or a numpy array")
+    if joint_qd is not None and not hasattr(joint_qd, "device") and not isinstance(joint_qd, np.ndarray):
+        raise TypeError("eval_ik: joint_qd must be a tensor or a numpy array")
+    qs, qds = cut(joint_q, "joint_coord_count"), cut(joint_qd, "joint_dof_count")
+    sels = [None] * len(parts) if art_sel is None else np.split(art_sel, np.cumsum([p.articulation_count for p in parts])[:-1])
+
+    def go(i, p):
+        eval_ik(p, state.parts[i], qs[i], qds[i], mask=sels[i])
+
+    if getattr(model, "is_gpu", False):
+        groups.run(go)
+    else:
+        for i, p in enumerate(parts):
+            go(i, p)

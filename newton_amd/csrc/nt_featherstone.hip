@@ -1,7 +1,178 @@
-// nt_featherstone.hip -- SolverFeatherstone (step / fused rollout) and eval_fk: launch code + C ABI.  The kernels are
+// nt_featherstone.hip -- SolverFeatherstone (step / fused rollout), eval_fk and eval_ik: launch code + C ABI.  The solver's kernels are
 // nt_featherstone_kernels.hpp, their phases nt_featherstone.hpp (namespace ieee); this unit exists so that they are compiled with the
-// default scheduler (see nt_step_preamble.hpp).
+// default scheduler (see nt_step_preamble.hpp).  eval_ik (kernel and entry points, include/newton_hip_kinematics.h) lives here whole:
+// the headers the stepping unit shares stay as they are.
 #include "nt_step_preamble.hpp"
+#ifndef NT_EMULATED_GRID
+#include "../../include/newton_hip_kinematics.h"
+#else  // (the CPU emulator compiles a copy of this file from tests/emu/_build)
+#include "../../../include/newton_hip_kinematics.h"
+#endif
+
+namespace {
+namespace ieee {
+
+// ------------------------------------------------------------------------------------------------
+// newton.eval_ik(model, state, joint_q, joint_qd) (newton/_src/sim/articulation.py): joint coordinates from body state, the algebraic
+// inverse of eval_fk_kernel / fs_fk_vel_item<PUBLIC>.  The joints of an environment do not depend on each other (a joint reads the
+// two bodies it connects), so there is no level loop: one (environment, joint) item per slot-lane between two barriers.
+// Tile: the persistent block of the XPBD layout without its body-derived tile (body state, parameters), then joint_q [nc] and
+// joint_qd [nd] rows that unstage_rows writes out.
+// ------------------------------------------------------------------------------------------------
+__host__ __device__ inline int ik_rows(const nt_model& m, const bool uni) {
+    return make_layout(m, false, false, uni, false).bd.off + m.nc + m.nd;
+}
+
+// twist angle of q about `axis`, in (-pi, pi]
+NT_DI float ik_twist_angle(vec3 axis, quat q) {
+    const float pi = 3.14159265358979323846f;
+    float t = 2.0f * atan2f(dot(axis, vec3(q.x, q.y, q.z)), q.w);
+    if (t > pi) t -= 2.0f * pi;
+    if (t <= -pi) t += 2.0f * pi;
+    return t;
+}
+
+template <int EPB>
+NT_DI void ik_joint_item(const Ctx<EPB>& c, int j, int oq, int oqd, const float* joint_q, const float* joint_qd) {
+    const nt_model& m = c.a.m;
+    const int parent = c.T.joint_parent[j], child = c.T.joint_child[j], type = c.T.joint_type[j];
+    const int qs = c.T.joint_q_start[j], ds = c.T.joint_qd_start[j];
+    const int lin = c.T.joint_lin_count[j], ang = c.T.joint_ang_count[j];
+    auto Q = [&](int i) -> float& { return c.lds[(oq + i) * Ctx<EPB>::N + c.e]; };
+    auto QD = [&](int i) -> float& { return c.lds[(oqd + i) * Ctx<EPB>::N + c.e]; };
+    const bool is_free = type == JT_FREE || type == JT_DISTANCE;
+    if (type != JT_PRISMATIC && type != JT_REVOLUTE && type != JT_BALL && type != JT_D6 && !is_free) {
+        // FIXED has no coordinates; a type eval_fk skips too keeps what the arrays hold
+        const int qe = j + 1 < m.nj ? c.T.joint_q_start[j + 1] : m.nc, de = j + 1 < m.nj ? c.T.joint_qd_start[j + 1] : m.nd;
+        for (int i = qs; i < qe; ++i) Q(i) = joint_q[(size_t)i * c.ES + c.env];
+        for (int i = ds; i < de; ++i) QD(i) = joint_qd[(size_t)i * c.ES + c.env];
+        return;
+    }
+    xform X_wpj = c.plxf(c.L.jp, 0, m.nj, j);
+    xform X_wp;
+    if (parent >= 0) {
+        X_wp = c.body_q(parent);
+        X_wpj = X_wp * X_wpj;
+    }
+    const xform X_wc = c.body_q(child);
+    const xform X_wcj = X_wc * c.plxf(c.L.jp, 7, m.nj, j);
+    // X_j = X_wpj^-1 X_wcj
+    const vec3 x_j = quat_rotate_inv(X_wpj.q, X_wcj.p - X_wpj.p);
+    const quat q_j = quat_inverse(X_wpj.q) * X_wcj.q;
+    // the joint's velocity in the parent anchor frame: fs_fk_vel_item<PUBLIC> undone term by term (body_qd carries the COM velocity)
+    const vec3 w_o = c.body_w(child), com_w = quat_rotate(X_wc.q, c.com(child));
+    const vec3 v_o = c.body_v(child) - cross(w_o, com_w);
+    vec3 w_parent, v_parent;
+    if (parent >= 0) {
+        w_parent = c.body_w(parent);
+        v_parent = cross(w_parent, X_wc.p - xform_point(X_wp, c.com(parent))) + c.body_v(parent);
+    }
+    const vec3 ang_w = w_o - w_parent, lin_origin = v_o - v_parent;
+    const vec3 lin_w = is_free ? lin_origin + cross(ang_w, com_w) : lin_origin - cross(ang_w, X_wc.p - X_wcj.p);
+    const vec3 v_lin = quat_rotate_inv(X_wpj.q, lin_w), v_ang = quat_rotate_inv(X_wpj.q, ang_w);
+
+    if (type == JT_PRISMATIC) {
+        Q(qs) = dot(c.dof_axis(ds), x_j);
+        QD(ds) = dot(c.dof_axis(ds), v_lin);
+    } else if (type == JT_REVOLUTE) {
+        Q(qs) = ik_twist_angle(c.dof_axis(ds), q_j);
+        QD(ds) = dot(c.dof_axis(ds), v_ang);
+    } else if (type == JT_BALL) {
+        Q(qs) = q_j.x; Q(qs + 1) = q_j.y; Q(qs + 2) = q_j.z; Q(qs + 3) = q_j.w;
+        QD(ds) = v_ang.x; QD(ds + 1) = v_ang.y; QD(ds + 2) = v_ang.z;
+    } else if (is_free) {
+        Q(qs) = x_j.x; Q(qs + 1) = x_j.y; Q(qs + 2) = x_j.z;
+        Q(qs + 3) = q_j.x; Q(qs + 4) = q_j.y; Q(qs + 5) = q_j.z; Q(qs + 6) = q_j.w;
+        QD(ds) = v_lin.x; QD(ds + 1) = v_lin.y; QD(ds + 2) = v_lin.z;
+        QD(ds + 3) = v_ang.x; QD(ds + 4) = v_ang.y; QD(ds + 5) = v_ang.z;
+    } else {  // D6
+        for (int k = 0; k < lin; ++k) {
+            Q(qs + k) = dot(c.dof_axis(ds + k), x_j);
+            QD(ds + k) = dot(c.dof_axis(ds + k), v_lin);
+        }
+        const int iq = qs + lin, id = ds + lin;
+        if (ang == 1) {
+            Q(iq) = ik_twist_angle(c.dof_axis(id), q_j);
+            QD(id) = dot(c.dof_axis(id), v_ang);
+        }
+        if (ang >= 2) {
+            // eval_fk composes q_2 q_1 q_0 about successively rotated axes = r_0 r_1 r_2 about the fixed (mutually orthogonal) axes:
+            // the angles are the intrinsic x-y-z Euler angles of M = B^T R(q_j) B, B = [e0 e1 e2] (a left-handed triple flips
+            // their signs); two axes: r_2 = 1 and both angles keep their full range
+            const vec3 e0 = c.dof_axis(id), e1 = c.dof_axis(id + 1);
+            const vec3 e2 = ang == 3 ? c.dof_axis(id + 2) : cross(e0, e1);
+            const vec3 r0 = quat_rotate(q_j, e0), r1 = quat_rotate(q_j, e1), r2 = quat_rotate(q_j, e2);
+            float t0, t1, t2 = 0.0f;
+            if (ang == 2) {
+                t0 = atan2f(dot(e2, r1), dot(e1, r1));
+                t1 = atan2f(dot(e0, r2), dot(e0, r0));
+            } else {
+                const float s = dot(cross(e0, e1), e2) < 0.0f ? -1.0f : 1.0f;
+                const float m00 = dot(e0, r0), m01 = dot(e0, r1), m02 = dot(e0, r2);
+                t0 = s * atan2f(-dot(e1, r2), dot(e2, r2));
+                t1 = s * atan2f(m02, sqrtf(m00 * m00 + m01 * m01));
+                t2 = s * atan2f(-m01, m00);
+            }
+            // rates: v_ang = a_0 qd_0 + a_1 qd_1 (+ a_2 qd_2) over eval_fk's transported axes at the recovered angles (Cramer)
+            vec3 a0, a1, a2;
+            d6_multi_angular(ang, e0, e1, ang == 3 ? e2 : vec3(), t0, t1, t2, a0, a1, a2);
+            Q(iq) = t0; Q(iq + 1) = t1;
+            if (ang == 2) {
+                const float g00 = dot(a0, a0), g01 = dot(a0, a1), g11 = dot(a1, a1), b0 = dot(a0, v_ang), b1 = dot(a1, v_ang);
+                const float det = g00 * g11 - g01 * g01;
+                QD(id) = (b0 * g11 - b1 * g01) / det;
+                QD(id + 1) = (g00 * b1 - g01 * b0) / det;
+            } else {
+                const vec3 a12 = cross(a1, a2);
+                const float det = dot(a0, a12);
+                Q(iq + 2) = t2;
+                QD(id) = dot(v_ang, a12) / det;
+                QD(id + 1) = dot(a0, cross(v_ang, a2)) / det;
+                QD(id + 2) = dot(a0, cross(a1, v_ang)) / det;
+            }
+        }
+    }
+}
+
+// art_mask: [env_count * na] or NULL (every joint).  A joint the mask leaves out is neither computed nor written.
+template <int EPB>
+__global__ void __launch_bounds__(256) eval_ik_kernel(KArgs a, float* joint_q, float* joint_qd, const uint8_t* art_mask) {
+    extern __shared__ __align__(16) float lds[];
+    const nt_model& m = a.m;
+    Ctx<EPB> c(a, lds, ik_rows(m, Ctx<EPB>::UNI));
+    load_state(c, a.s_in);
+    load_params(c, false);
+    __syncthreads();  // (topology ints, tile)
+    const int oq = c.L.bd.off, oqd = oq + m.nc;
+    if (c.valid) {
+        if (!art_mask) {
+            for (int j = c.slot; j < m.nj; j += c.nslot) ik_joint_item(c, j, oq, oqd, joint_q, joint_qd);
+        } else {  // the joints of the selected articulations; joints outside any articulation never are
+            for (int k = 0; k < m.na; ++k)
+                if (art_mask[(size_t)c.env * m.na + k])
+                    for (int j = m.art_start[k] + c.slot; j < m.art_start[k + 1]; j += c.nslot)
+                        ik_joint_item(c, j, oq, oqd, joint_q, joint_qd);
+        }
+    }
+    __syncthreads();
+    if (!c.valid) return;
+    if (!art_mask) {
+        unstage_rows(c, oq, joint_q, m.nc);
+        unstage_rows(c, oqd, joint_qd, m.nd);
+        return;
+    }
+    for (int k = 0; k < m.na; ++k) {  // the coordinates of an articulation are one row range
+        const int j0 = m.art_start[k], j1 = m.art_start[k + 1];
+        if (j0 >= j1 || !art_mask[(size_t)c.env * m.na + k]) continue;
+        const int q0 = c.T.joint_q_start[j0], q1 = j1 < m.nj ? c.T.joint_q_start[j1] : m.nc;
+        const int d0 = c.T.joint_qd_start[j0], d1 = j1 < m.nj ? c.T.joint_qd_start[j1] : m.nd;
+        unstage_rows(c, oq + q0, joint_q + (size_t)q0 * c.ES, q1 - q0);
+        unstage_rows(c, oqd + d0, joint_qd + (size_t)d0 * c.ES, d1 - d0);
+    }
+}
+
+}  // namespace ieee
+}  // namespace
 
 extern "C" {
 
@@ -127,6 +298,49 @@ nt_status nt_eval_fk(const nt_model* m, const float* joint_q, const float* joint
 #endif
 }
 
+// widest tile that fits (0), or the per-environment-parameter tile of 1 / 4 / 8 / 16 environments the caller names
+nt_status nt_eval_ik_tile(const nt_model* m, const nt_state* in, float* joint_q, float* joint_qd, const uint8_t* art_mask,
+                          int32_t envs_per_block, void* stream) {
+    if (!model_ok(m) || !in || !in->body_q || !in->body_qd || !joint_q || !joint_qd) return NT_ERR_INVALID_ARG;
+    if (m->nj <= 0) return NT_ERR_UNSUPPORTED;
+#ifdef NT_DEV_FAST
+    return NT_ERR_UNSUPPORTED;
+#else
+    KArgs a = {};
+    a.m = *m;
+    a.s_in = *in;
+    const size_t shared_ints = (size_t)topo_ints(*m);
+    auto bytes = [&](int epb, bool uni) {
+        return tile_bytes(ik_rows(*m, uni), epb, shared_ints, uni ? make_layout(*m, false, false, true, false).uni_floats : 0);
+    };
+    // replicated worlds (nt_model.params_uniform): ONE block-shared parameter copy -- the parameters are four fifths of what the
+    // per-environment tile reads
+    const bool uni = envs_per_block == 0 && m->params_uniform && bytes(16, true) <= LDS_BYTES_PER_CU;
+    int epb = 0;
+    if (uni) {
+        epb = 16;
+    } else if (envs_per_block == 0) {
+        const int cands[4] = {16, 8, 4, 1};
+        for (int i = 0; i < 4 && !epb; ++i)
+            if (bytes(cands[i], false) <= LDS_BYTES_PER_CU) epb = cands[i];
+    } else if ((envs_per_block == 1 || envs_per_block == 4 || envs_per_block == 8 || envs_per_block == 16) &&
+               bytes(envs_per_block, false) <= LDS_BYTES_PER_CU) {
+        epb = envs_per_block;
+    }
+    if (!epb) return NT_ERR_UNSUPPORTED;
+    const int want = imax(m->nb, m->nj), cap = 256 / epb;
+    a.nslot = want < cap ? want : cap;
+    if (uni)
+        return launch_tile(eval_ik_kernel<16 + NT_UNI>, a, 16, bytes(16, true), (hipStream_t)stream, joint_q, joint_qd, art_mask);
+    return dispatch_epb(Epbs<16, 8, 4, 1>{}, epb, [&](auto E) {
+        return launch_tile(eval_ik_kernel<E>, a, E, bytes(E, false), (hipStream_t)stream, joint_q, joint_qd, art_mask);
+    });
+#endif
+}
+
+nt_status nt_eval_ik(const nt_model* m, const nt_state* in, float* joint_q, float* joint_qd, const uint8_t* art_mask, void* stream) {
+    return nt_eval_ik_tile(m, in, joint_q, joint_qd, art_mask, 0, stream);
+}
 
 #ifdef NT_PHASE_TIMING
 // debug build only: read and reset this unit's phase cycle counters (the counters are per translation unit)

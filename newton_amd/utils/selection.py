@@ -1,6 +1,6 @@
 """ArticulationView -- the subset of newton.selection.ArticulationView (newton/_src/utils/selection.py:500-1800) that an RL
 loop calls between steps: per-world getters / setters for root pose and twist, dof positions / velocities / forces and
-link poses, with an optional world mask, plus masked eval_fk.
+link poses, with an optional world mask, plus masked eval_fk / eval_ik.
 
 With the env-major SoA layout these are not gather/scatter kernels: ``State._soa[name]`` has shape
 ``[comp, slots_per_env, env_stride]``, so "the dofs of every world" is a strided *view* ``soa[0, a:b, :E].T`` (no copy on
@@ -13,7 +13,7 @@ import fnmatch
 
 import numpy as np
 
-from ..articulation import eval_fk
+from ..articulation import eval_fk, eval_ik
 from ..enums import JointType
 
 
@@ -186,3 +186,14 @@ class ArticulationView:
             sel = m.repeat_interleave(nb)
             state.body_q = torch.where(sel[:, None], new_q, keep_q)
             state.body_qd = torch.where(sel[:, None], new_qd, keep_qd)
+
+    def eval_ik(self, state, mask=None):
+        """newton.eval_ik restricted to the selected worlds: joint_q / joint_qd of unselected worlds are left untouched.  The dof
+        getters return the state's joint arrays, which the maximal-coordinate solvers do not advance: call this after stepping."""
+        if mask is None:
+            eval_ik(self.model, state)
+            return
+        na = self.model.env.na
+        probe = state._soa["joint_q"] if getattr(self.model, "is_gpu", False) and hasattr(state, "_soa") else np.empty(0)
+        m = self._mask(mask, probe)
+        eval_ik(self.model, state, mask=m.repeat_interleave(na) if hasattr(m, "repeat_interleave") else np.repeat(m, na))

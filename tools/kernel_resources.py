@@ -13,17 +13,20 @@ lib = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "newton_amd", "li
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
 LLVM = "/opt/rocm/lib/llvm/bin"
 with tempfile.TemporaryDirectory() as d:
-    subprocess.run([f"{LLVM}/clang-offload-bundler", "--list", "--type=o", f"--input={lib}"], capture_output=True)
-    # the fat binary sits in .hip_fatbin: unbundle the gfx950 code object
-    out = os.path.join(d, "co")
-    r = subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={lib}", f"--output={out}",
-                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950"], capture_output=True, text=True)
-    if r.returncode != 0 or not os.path.exists(out):
-        fb = os.path.join(d, "fb")
-        subprocess.run([f"{LLVM}/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib, fb], check=True)
-        subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fb}", f"--output={out}",
+    # every translation unit leaves a bundle of its own in .hip_fatbin: unbundle the gfx950 code object of each.  (Unbundling the
+    # library file itself finds no bundle with this toolchain, and unbundling the whole section yields the first unit only -- the
+    # stepping unit, without the Featherstone / eval_fk / eval_ik kernels -- hence the split at the bundle magic.)
+    fb = os.path.join(d, "fb")
+    subprocess.run([f"{LLVM}/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib, fb], check=True)
+    data, magic, notes = open(fb, "rb").read(), b"__CLANG_OFFLOAD_BUNDLE__", ""
+    starts = [m.start() for m in re.finditer(magic, data)]
+    for i, (a, b) in enumerate(zip(starts, starts[1:] + [len(data)])):
+        part, out = os.path.join(d, f"fb{i}"), os.path.join(d, f"co{i}")
+        with open(part, "wb") as f:
+            f.write(data[a:b])
+        subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={part}", f"--output={out}",
                         "--targets=hipv4-amdgcn-amd-amdhsa--gfx950"], check=True)
-    notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", out], capture_output=True, text=True).stdout
+        notes += subprocess.run([f"{LLVM}/llvm-readelf", "--notes", out], capture_output=True, text=True).stdout
 rows = []
 for blk in notes.split("  - .agpr_count:")[1:]:
     g = lambda k: (re.search(rf"\.{k}:\s+(\S+)", blk) or [None, "?"])[1]  # noqa: E731
