@@ -50,6 +50,15 @@ def main():
     newton.eval_ik(model, state_0)
     dof_q = newton.selection.ArticulationView(model, "*").get_dof_positions(state_0)
     print(f"dof positions after the last frame: leg joints within [{float(dof_q[:, 7:].min()):.3f}, {float(dof_q[:, 7:].max()):.3f}] rad")
+    # what a task-space controller asks for next: the Jacobian (joint_q is current after eval_ik) and one J^T f -- the generalized
+    # forces of a 10 N vertical force at the origin of the last link (a foot).  Rows are origin-referenced twists, so the force
+    # enters as the wrench (f, p x f) about the world origin
+    view = newton.selection.ArticulationView(model, "*")
+    J, H = view.eval_jacobian(state_0), view.eval_mass_matrix(state_0)
+    foot = J[:, 6 * (view.link_count - 1):6 * view.link_count, :]
+    p = view.get_link_transforms(state_0)[:, -1, :3]
+    tau = 10.0 * (foot[:, 2, :] + p[:, 1:2] * foot[:, 3, :] - p[:, 0:1] * foot[:, 4, :])
+    print(f"Jacobian {tuple(J.shape)}, mass matrix {tuple(H.shape)}; J^T f of the last foot: max generalized force {float(abs(tau).max()):.3f}")
 
 
 if __name__ == "__main__":

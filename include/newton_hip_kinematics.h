@@ -51,6 +51,55 @@ nt_status nt_eval_ik(const nt_model* m, const nt_state* in, float* joint_q /*[nc
 nt_status nt_eval_ik_tile(const nt_model* m, const nt_state* in, float* joint_q, float* joint_qd, const uint8_t* art_mask,
                           int32_t envs_per_block, void* stream);
 
+/* Articulation Jacobian and joint-space inertia (paths relative to the Newton source tree):
+ *   nt_eval_jacobian      <- newton.eval_jacobian(model, state, J, joint_S_s, mask)                      newton/_src/sim/articulation.py
+ *   nt_eval_mass_matrix   <- newton.eval_mass_matrix(model, state, H, J, body_I_s, joint_S_s, mask)      newton/_src/sim/articulation.py
+ *
+ * Layout (public, NOT environment-major): articulation a = world * nt_model.na + k; L = the widest articulation in joints (max over k
+ * of art_start[k + 1] - art_start[k]), D = nt_model.max_art_dofs.
+ *   J         [env_count * na][6 L][D]   row block i of articulation a: the child body of joint art_start[k] + i; column c: the dof
+ *                                        joint_qd_start[art_start[k]] + c of that world
+ *   joint_S_s [env_count * nd][6]        the column of each dof (optional)
+ *   H         [env_count * na][D][D]     joint-space inertia, both triangles
+ *   body_I_s  [env_count * nb][6][6]     each link's world-frame spatial inertia about the origin (optional; bodies that are no joint's
+ *                                        child are not written)
+ * Padding rows / columns (an articulation narrower than L / D) and the entries of dofs that are not on a link's root path are written
+ * as zero by every call: no memset is needed.
+ *
+ * Rows are origin-referenced world twists, linear first.  Columns are with respect to the public joint_qd (a FREE / DISTANCE joint
+ * carries its child's COM velocity).  The defining identity, with nt_eval_fk: for link l with world pose (x_l, q_l), COM
+ * c_l = x_l + rot(q_l, com_l) and (v, w) = J[a, 6 i : 6 i + 6, :] joint_qd[dofs of a], eval_fk's body_qd[l] = (v + w x c_l, w).
+ * Column d of link l is S_d when d belongs to l's joint or to a joint on its joint_parent chain inside the articulation (a FREE child
+ * in mid-chain inherits its ancestors' columns), else 0.  With X_wpj = body_q[parent] X_p = (p, R) and p_j the position of
+ * X_wcj = X_wpj X_j(joint_q):
+ *   PRISMATIC  (R a, 0)                REVOLUTE  (p_j x R a, R a)            BALL  (p_j x R e_k, R e_k)            FIXED  none
+ *   D6         linear axes as PRISMATIC; angular axes: eval_fk's successively rotated axes a_0, a_1, a_2 (they depend on the joint's
+ *              own joint_q), about p_j
+ *   FREE / DISTANCE  linear (R e_k, 0); angular (c_child x R e_k, R e_k) -- about the child's COM
+ * H = sum over links of J_l^T I_l J_l, I_l the link's spatial inertia: q'^T H q' / 2 is the articulation's kinetic energy
+ * sum m |v_com|^2 / 2 + w^T R I R^T w / 2 with eval_fk's body_qd.  Symmetric bit for bit.  NO armature is added: this is not the matrix
+ * nt_featherstone_step factorises (that one carries nt_model's dof armature on its diagonal and the solver's internal FREE-joint
+ * velocity convention).  Computed from composite inertias along the tree in a fixed order, without atomics, about the articulation's
+ * root link position (H does not depend on the point).
+ *
+ * Inputs read: in->body_q (parent poses, link COMs) and in->joint_q (the joint's own displacement: D6 pivots and rotated axes) --
+ * eval_fk's composition.  After a maximal-coordinate step call nt_eval_ik first, so that joint_q matches body_q.  in->body_qd is not
+ * read.
+ *
+ * art_mask as for nt_eval_ik, with the same contiguity precondition: the slices of unselected articulations in every output are
+ * neither computed nor written.  One launch each, no scratch state, no allocation, no synchronisation; recordable by
+ * nt_graph_capture_begin / _end.  Errors: null m / in / body_q / joint_q / J / H NT_ERR_INVALID_ARG; nj <= 0, na <= 0, a tile that does
+ * not fit the CU's LDS, an envs_per_block other than 0 / 1 / 4 / 8 / 16, a build with NT_DEV_FAST: NT_ERR_UNSUPPORTED.  The _tile
+ * forms name the tile as nt_eval_ik_tile does; every tile computes the same bits. */
+nt_status nt_eval_jacobian(const nt_model* m, const nt_state* in, float* J, float* joint_S_s /*or NULL*/,
+                           const uint8_t* art_mask /*[env_count*na] or NULL*/, void* stream);
+nt_status nt_eval_jacobian_tile(const nt_model* m, const nt_state* in, float* J, float* joint_S_s, const uint8_t* art_mask,
+                                int32_t envs_per_block, void* stream);
+nt_status nt_eval_mass_matrix(const nt_model* m, const nt_state* in, float* H, float* body_I_s /*or NULL*/,
+                              const uint8_t* art_mask /*[env_count*na] or NULL*/, void* stream);
+nt_status nt_eval_mass_matrix_tile(const nt_model* m, const nt_state* in, float* H, float* body_I_s, const uint8_t* art_mask,
+                                   int32_t envs_per_block, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

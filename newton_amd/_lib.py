@@ -433,6 +433,10 @@ SYMBOLS = {
     # include/newton_hip_kinematics.h
     "nt_eval_ik": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_state), _P, _P, _P, _P]),
     "nt_eval_ik_tile": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_state), _P, _P, _P, C.c_int32, _P]),
+    "nt_eval_jacobian": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_state), _P, _P, _P, _P]),
+    "nt_eval_jacobian_tile": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_state), _P, _P, _P, C.c_int32, _P]),
+    "nt_eval_mass_matrix": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_state), _P, _P, _P, _P]),
+    "nt_eval_mass_matrix_tile": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_state), _P, _P, _P, C.c_int32, _P]),
     "nt_hydro_collide": (C.c_int32, [C.POINTER(nt_hydro_args), _P]),
     "nt_hydro_pairs": (C.c_int32, [C.POINTER(nt_hydro_args), _P]),
     "nt_sdf_candidate_pairs": (C.c_int32, [C.POINTER(nt_sdf_scene), _P, _P, _P, _P, _P, _P]),

@@ -539,3 +539,401 @@ def _eval_ik_groups(model, state, joint_q, joint_qd, art_sel):
     else:
         for i, p in enumerate(parts):
             go(i, p)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# eval_jacobian / eval_mass_matrix
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _articulated(model, what):
+    t = model.env
+    if t.nj == 0 or t.na == 0:
+        raise NotImplementedError(f"{what}: needs articulations that cover every world's joints in order (unsupported)")
+    return t
+
+
+def _joint_ancestors(t):
+    """Per env-local joint: the joint of the same articulation whose child is its parent body (-1: none)."""
+    art = np.searchsorted(t.art_start[1:], np.arange(t.nj), side="right")
+    anc = -np.ones(t.nj, dtype=np.int64)
+    for j in range(t.nj):
+        p = int(t.joint_parent[j])
+        if p >= 0:
+            for k in range(int(t.art_start[art[j]]), int(t.art_start[art[j] + 1])):
+                if int(t.joint_child[k]) == p:
+                    anc[j] = k
+    return art, anc
+
+
+def _path_matrix(t):
+    """bool [nj, nj]: entry (l, a) -- joint a is joint l or on its joint_parent chain inside the articulation."""
+    _, anc = _joint_ancestors(t)
+    on = np.zeros((t.nj, t.nj), dtype=bool)
+    for j in range(t.nj):
+        k, n = j, 0
+        while k >= 0 and n <= t.nj:
+            on[j, k] = True
+            k, n = anc[k], n + 1
+    return on
+
+
+def _motion_subspace_numpy(model, body_q, joint_q):
+    """S [E, nd, 6] in float64: the column of every dof as an origin-referenced world twist (linear, angular) -- the closed forms of
+    include/newton_hip_kinematics.h."""
+    t = model.env
+    E, nb, nj = t.env_count, t.nb, t.nj
+    bq = np.asarray(body_q, dtype=np.float64).reshape(E, nb, 7)
+    jq = np.asarray(joint_q, dtype=np.float64).reshape(E, t.nc)
+    com = np.asarray(model.body_com, dtype=np.float64).reshape(E, nb, 3)
+    X_p = np.asarray(model.joint_X_p, dtype=np.float64).reshape(E, nj, 7)
+    axis_all = np.asarray(model.joint_axis, dtype=np.float64).reshape(E, t.nd, 3)
+    S = np.zeros((E, t.nd, 6))
+    eye = np.eye(3)
+    for j in range(nj):
+        jt = int(t.joint_type[j])
+        parent, child = int(t.joint_parent[j]), int(t.joint_child[j])
+        qs, ds = int(t.joint_q_start[j]), int(t.joint_qd_start[j])
+        lin, ang = int(t.joint_lin_count[j]), int(t.joint_ang_count[j])
+        X_wpj = X_p[:, j]
+        if parent >= 0:
+            X_wpj = _xmul(bq[:, parent], X_wpj)
+        p, qR = X_wpj[:, :3], X_wpj[:, 3:]
+
+        def linear(d, a):
+            S[:, d, :3] = _qrot(qR, a)
+
+        def angular(d, a, pivot):
+            w = _qrot(qR, a)
+            S[:, d, :3], S[:, d, 3:] = np.cross(pivot, w), w
+
+        unit = lambda k: np.broadcast_to(eye[k], (E, 3))  # noqa: E731
+        if jt == JointType.PRISMATIC:
+            linear(ds, axis_all[:, ds])
+        elif jt == JointType.REVOLUTE:
+            angular(ds, axis_all[:, ds], p)
+        elif jt == JointType.BALL:
+            for k in range(3):
+                angular(ds + k, unit(k), p)
+        elif jt in (JointType.FREE, JointType.DISTANCE):
+            c_child = bq[:, child, :3] + _qrot(bq[:, child, 3:], com[:, child])
+            for k in range(3):
+                linear(ds + k, unit(k))
+                angular(ds + 3 + k, unit(k), c_child)
+        elif jt == JointType.D6:
+            pos = np.zeros((E, 3))
+            for k in range(lin):
+                linear(ds + k, axis_all[:, ds + k])
+                pos += axis_all[:, ds + k] * jq[:, qs + k:qs + k + 1]
+            p_j = p + _qrot(qR, pos)
+            e = [axis_all[:, ds + lin + k] for k in range(ang)]
+            if ang == 1:
+                a = [e[0]]
+            elif ang == 2:  # compute_2d_rotational_dofs, as eval_fk_numpy
+                q_off = _quat_from_cols(e[0], e[1], np.cross(e[0], e[1]))
+                a0 = _qrot(q_off, unit(0))
+                a = [a0, _qrot(_quat_axis_angle(a0, jq[:, qs + lin]), _qrot(q_off, unit(1)))]
+            elif ang == 3:
+                q_0 = _quat_axis_angle(e[0], jq[:, qs + lin])
+                a1 = _qrot(q_0, e[1])
+                a = [e[0], a1, _qrot(_qmul(_quat_axis_angle(a1, jq[:, qs + lin + 1]), q_0), e[2])]
+            else:
+                a = []
+            for k in range(ang):
+                angular(ds + lin + k, a[k], p_j)
+    return S
+
+
+def _spatial_inertia_numpy(model, body_q):
+    """[E, nb, 6, 6] in float64: each body's world-frame spatial inertia about the origin, (linear, angular) ordering."""
+    t = model.env
+    E, nb = t.env_count, t.nb
+    bq = np.asarray(body_q, dtype=np.float64).reshape(E, nb, 7)
+    com = np.asarray(model.body_com, dtype=np.float64).reshape(E, nb, 3)
+    mass = np.asarray(model.body_mass, dtype=np.float64).reshape(E, nb)
+    Ib = np.asarray(model.body_inertia, dtype=np.float64).reshape(E, nb, 3, 3)
+    q = bq.reshape(-1, 7)[:, 3:]
+    R = np.stack([_qrot(q, np.broadcast_to(np.eye(3)[k], (E * nb, 3))) for k in range(3)], axis=-1).reshape(E, nb, 3, 3)
+    c = bq[:, :, :3] + _qrot(q, com.reshape(-1, 3)).reshape(E, nb, 3)
+    cx = np.zeros((E, nb, 3, 3))
+    cx[..., 0, 1], cx[..., 0, 2], cx[..., 1, 0] = -c[..., 2], c[..., 1], c[..., 2]
+    cx[..., 1, 2], cx[..., 2, 0], cx[..., 2, 1] = -c[..., 0], -c[..., 1], c[..., 0]
+    m = mass[..., None, None]
+    out = np.zeros((E, nb, 6, 6))
+    out[..., :3, :3] = m * np.eye(3)
+    out[..., :3, 3:] = -m * cx
+    out[..., 3:, :3] = m * cx
+    out[..., 3:, 3:] = R @ Ib @ np.swapaxes(R, -1, -2) - m * (cx @ cx)
+    return out
+
+
+def _art_dims(model):
+    return int(model.max_joints_per_articulation), int(model.max_dofs_per_articulation)
+
+
+def _art_ranges(t):
+    """Per env-local articulation: (first joint, joint count, first dof, dof count)."""
+    dof_edges = np.concatenate([t.joint_qd_start, [t.nd]])
+    return [(int(t.art_start[k]), int(t.art_start[k + 1] - t.art_start[k]), int(dof_edges[t.art_start[k]]),
+             int(dof_edges[t.art_start[k + 1]] - dof_edges[t.art_start[k]])) for k in range(t.na)]
+
+
+def _new_or_checked(out, shape, what):
+    if out is None:
+        return np.zeros(shape, dtype=np.float32)
+    if not isinstance(out, np.ndarray) or out.dtype != np.float32 or tuple(out.shape) != tuple(shape):
+        raise ValueError(f"{what} must be a float32 numpy array of shape {tuple(shape)}")
+    return out
+
+
+def eval_jacobian_numpy(model, body_q, joint_q, J=None, joint_S_s=None, art_sel=None):
+    """Host mirror of eval_jacobian_kernel (float64 inside, float32 out): fills and returns J [articulation_count, 6 L, D]; the slices
+    of articulations ``art_sel`` (bool per articulation) leaves out stay untouched, in ``joint_S_s`` [joint_dof_count, 6] too."""
+    L, D = _art_dims(model)
+    J = _new_or_checked(J, (int(model.articulation_count), 6 * L, D), "J")
+    if joint_S_s is not None:
+        joint_S_s = _new_or_checked(joint_S_s, (int(model.joint_dof_count), 6), "joint_S_s")
+    if getattr(model, "is_heterogeneous", False):
+        parts = model.world_groups.parts
+        bqs = np.split(np.asarray(body_q).reshape(-1, 7), np.cumsum([p.body_count for p in parts])[:-1])
+        jqs = np.split(np.asarray(joint_q).reshape(-1), np.cumsum([p.joint_coord_count for p in parts])[:-1])
+        a0 = d0 = 0
+        for p, bq, jq in zip(parts, bqs, jqs):
+            a1, d1 = a0 + p.articulation_count, d0 + p.joint_dof_count
+            if p.articulation_count:
+                sel = None if art_sel is None else np.asarray(art_sel, dtype=bool)[a0:a1]
+                Lp, Dp = _art_dims(p)
+                Jp = np.array(J[a0:a1, :6 * Lp, :Dp])  # (a copy: the slice is cleared below)
+                eval_jacobian_numpy(p, bq, jq, Jp, None if joint_S_s is None else joint_S_s[d0:d1], sel)
+                rows = slice(a0, a1) if sel is None else a0 + np.flatnonzero(sel)
+                J[rows] = 0.0
+                J[rows, :6 * Lp, :Dp] = Jp if sel is None else Jp[sel]
+            a0, d0 = a1, d1
+        return J
+    t = _articulated(model, "eval_jacobian")
+    E = t.env_count
+    S = _motion_subspace_numpy(model, body_q, joint_q)
+    on = _path_matrix(t)
+    dof_joint = np.searchsorted(t.joint_qd_start, np.arange(t.nd), side="right") - 1 if t.nd else np.zeros(0, dtype=np.int64)
+    sel = np.ones((E, t.na), dtype=bool) if art_sel is None else np.asarray(art_sel, dtype=bool).reshape(E, t.na)
+    Jv = J.reshape(E, t.na, 6 * L, D)
+    for k, (j0, nja, d0, nda) in enumerate(_art_ranges(t)):
+        blk = np.zeros((E, 6 * L, D))
+        for i in range(nja):
+            cols = on[j0 + i, dof_joint[d0:d0 + nda]]
+            blk[:, 6 * i:6 * i + 6, :nda] = np.swapaxes(S[:, d0:d0 + nda], 1, 2) * cols
+        Jv[sel[:, k], k] = blk[sel[:, k]].astype(np.float32)
+        if joint_S_s is not None:
+            joint_S_s.reshape(E, t.nd, 6)[sel[:, k], d0:d0 + nda] = S[sel[:, k], d0:d0 + nda].astype(np.float32)
+    return J
+
+
+def eval_mass_matrix_numpy(model, body_q, joint_q, H=None, body_I_s=None, art_sel=None):
+    """Host mirror of eval_mass_matrix_kernel: H [articulation_count, D, D] = sum over links of J_l^T I_l J_l, in float64 from the
+    definition (the kernel composes inertias along the tree), float32 out; ``body_I_s`` [body_count, 6, 6] optional."""
+    L, D = _art_dims(model)
+    H = _new_or_checked(H, (int(model.articulation_count), D, D), "H")
+    if body_I_s is not None:
+        body_I_s = _new_or_checked(body_I_s, (int(model.body_count), 6, 6), "body_I_s")
+    if getattr(model, "is_heterogeneous", False):
+        parts = model.world_groups.parts
+        bqs = np.split(np.asarray(body_q).reshape(-1, 7), np.cumsum([p.body_count for p in parts])[:-1])
+        jqs = np.split(np.asarray(joint_q).reshape(-1), np.cumsum([p.joint_coord_count for p in parts])[:-1])
+        a0 = b0 = 0
+        for p, bq, jq in zip(parts, bqs, jqs):
+            a1, b1 = a0 + p.articulation_count, b0 + p.body_count
+            if p.articulation_count:
+                sel = None if art_sel is None else np.asarray(art_sel, dtype=bool)[a0:a1]
+                Dp = _art_dims(p)[1]
+                Hp = np.array(H[a0:a1, :Dp, :Dp])
+                eval_mass_matrix_numpy(p, bq, jq, Hp, None if body_I_s is None else body_I_s[b0:b1], sel)
+                rows = slice(a0, a1) if sel is None else a0 + np.flatnonzero(sel)
+                H[rows] = 0.0
+                H[rows, :Dp, :Dp] = Hp if sel is None else Hp[sel]
+            a0, b0 = a1, b1
+        return H
+    t = _articulated(model, "eval_mass_matrix")
+    E = t.env_count
+    S = _motion_subspace_numpy(model, body_q, joint_q)
+    I_s = _spatial_inertia_numpy(model, body_q)
+    on = _path_matrix(t)
+    dof_joint = np.searchsorted(t.joint_qd_start, np.arange(t.nd), side="right") - 1 if t.nd else np.zeros(0, dtype=np.int64)
+    sel = np.ones((E, t.na), dtype=bool) if art_sel is None else np.asarray(art_sel, dtype=bool).reshape(E, t.na)
+    Hv = H.reshape(E, t.na, D, D)
+    for k, (j0, nja, d0, nda) in enumerate(_art_ranges(t)):
+        blk = np.zeros((E, D, D))
+        for i in range(nja):
+            Jl = np.swapaxes(S[:, d0:d0 + nda], 1, 2) * on[j0 + i, dof_joint[d0:d0 + nda]]  # [E, 6, nda]
+            b = int(t.joint_child[j0 + i])
+            blk[:, :nda, :nda] += np.swapaxes(Jl, 1, 2) @ I_s[:, b] @ Jl
+            if body_I_s is not None:
+                body_I_s.reshape(E, t.nb, 6, 6)[sel[:, k], b] = I_s[sel[:, k], b].astype(np.float32)
+        blk = 0.5 * (blk + np.swapaxes(blk, 1, 2))  # (symmetric bit for bit, like the kernel's one value per pair)
+        Hv[sel[:, k], k] = blk[sel[:, k]].astype(np.float32)
+    return H
+
+
+def _device_art_mask(model, art_sel, what):
+    if art_sel is None:
+        return None
+    import torch  # noqa: PLC0415
+
+    t = model.env
+    if t.na * t.env_count != art_sel.shape[0]:
+        raise NotImplementedError(f"{what}: mask needs articulations that cover every world's joints in order")
+    return torch.from_numpy(art_sel.astype(np.uint8)).to(model.device_model().device)
+
+
+def _device_out(model, out, shape, what):
+    """The caller's float32 device tensor (checked), or a new one."""
+    import torch  # noqa: PLC0415
+
+    dev = model.device_model().device
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    if not (hasattr(out, "data_ptr") and out.dtype == torch.float32 and out.is_cuda and out.is_contiguous()
+            and tuple(out.shape) == tuple(shape)):
+        raise ValueError(f"{what} must be a contiguous float32 tensor of shape {tuple(shape)} on the model's device")
+    return out
+
+
+def _mask_selection(model, mask, what):
+    art_sel = None
+    if mask is not None:
+        art_sel = _articulation_selection(model, mask, None, what)
+        if art_sel.all():
+            art_sel = None
+    return art_sel
+
+
+def _group_slices(model, out, sizes, art_axis_dims):
+    """Per world group the slice of a global output that belongs to it (first axis), or None."""
+    edges = np.concatenate([[0], np.cumsum(sizes)])
+    return [None if out is None else out[edges[i]:edges[i + 1]] for i in range(len(sizes))]
+
+
+def eval_jacobian(model, state, J=None, joint_S_s=None, mask=None):
+    """newton.eval_jacobian(model, state, J=None, joint_S_s=None, mask=None) (newton/_src/sim/articulation.py): the articulation
+    Jacobian ``J`` [articulation_count, 6 L, D] float32, L = ``model.max_joints_per_articulation``, D =
+    ``model.max_dofs_per_articulation``.  Row block i of articulation a is the child body of its joint i, an origin-referenced world
+    twist (linear first); column k is its dof k, with respect to the public ``joint_qd`` (a FREE / DISTANCE joint carries the COM
+    velocity).  With ``(v, w) = J[a, 6 i:6 i + 6] @ joint_qd[dofs of a]`` the body velocity :func:`eval_fk` produces is
+    ``(v + w x c, w)``, c the link's world COM.  Padding and the entries of dofs off a link's root path are written as zero on every
+    call.  ``joint_S_s`` [joint_dof_count, 6] (optional) receives the column of each dof; ``mask`` (bool per articulation) leaves the
+    slices of unselected articulations untouched.
+
+    Reads ``state.body_q`` (parent poses, COMs) and ``state.joint_q`` (the joint's own displacement) -- eval_fk's composition: after a
+    maximal-coordinate step (SolverXPBD, SolverSemiImplicit) call :func:`eval_ik` first.  Outputs left ``None`` are allocated and
+    returned: torch tensors on a GPU model, numpy arrays on a host model.  On a GPU model with ``J`` (and ``joint_S_s``, if wanted)
+    supplied and no ``mask`` the call is one kernel launch on the model's stream (nt_eval_jacobian): no allocation, no
+    synchronisation, it records into ``newton_amd.graph.capture``.  A mask uploads its bytes on every call."""
+    art_sel = _mask_selection(model, mask, "eval_jacobian")
+    if getattr(model, "is_heterogeneous", False):
+        return _eval_jm_groups(model, state, "jacobian", J, joint_S_s, art_sel)
+    L, D = _art_dims(model)
+    if not getattr(model, "is_gpu", False):
+        return eval_jacobian_numpy(model, _host_array(state.body_q), _host_array(state.joint_q), J, joint_S_s, art_sel)
+    t = _articulated(model, "eval_jacobian")
+    import ctypes as C  # noqa: PLC0415
+
+    from . import _lib  # noqa: PLC0415
+
+    dm = model.device_model()
+    fresh = J is None
+    J = _device_out(model, J, (t.env_count * t.na, 6 * L, D), "J")
+    if joint_S_s is not None:
+        joint_S_s = _device_out(model, joint_S_s, (t.env_count * t.nd, 6), "joint_S_s")
+    if fresh and art_sel is not None:
+        J.zero_()
+    art_mask = _device_art_mask(model, art_sel, "eval_jacobian")
+    d = state._desc()
+    _lib.check(dm.lib.nt_eval_jacobian(C.byref(dm.desc), C.byref(d), J.data_ptr(), None if joint_S_s is None else joint_S_s.data_ptr(),
+                                       None if art_mask is None else art_mask.data_ptr(), dm.stream()), "nt_eval_jacobian")
+    return J
+
+
+def eval_mass_matrix(model, state, H=None, J=None, body_I_s=None, joint_S_s=None, mask=None):
+    """newton.eval_mass_matrix(model, state, H=None, J=None, body_I_s=None, joint_S_s=None, mask=None)
+    (newton/_src/sim/articulation.py): the joint-space inertia ``H`` [articulation_count, D, D] float32, ``H = sum_l J_l^T I_l J_l``
+    with I_l the link's world-frame spatial inertia -- ``qd^T H qd / 2`` is the articulation's kinetic energy for the ``body_qd``
+    :func:`eval_fk` produces.  Symmetric bit for bit, both triangles written, padding zero.  No armature is added: this is NOT the
+    matrix SolverFeatherstone factorises (that one carries the dof armature and the solver's internal FREE-joint convention).
+    ``body_I_s`` [body_count, 6, 6] (optional) receives each link's spatial inertia about the world origin.  ``J`` / ``joint_S_s``, if
+    given, are filled by an additional :func:`eval_jacobian` launch; H itself is one launch of its own (nt_eval_mass_matrix) and never
+    reads J.  Inputs, allocation, ``mask`` and capture behaviour as for :func:`eval_jacobian` (after a maximal-coordinate step call
+    :func:`eval_ik` first)."""
+    art_sel = _mask_selection(model, mask, "eval_mass_matrix")
+    if J is not None or joint_S_s is not None:
+        eval_jacobian(model, state, J, joint_S_s, mask)
+    if getattr(model, "is_heterogeneous", False):
+        return _eval_jm_groups(model, state, "mass_matrix", H, body_I_s, art_sel)
+    D = _art_dims(model)[1]
+    if not getattr(model, "is_gpu", False):
+        return eval_mass_matrix_numpy(model, _host_array(state.body_q), _host_array(state.joint_q), H, body_I_s, art_sel)
+    t = _articulated(model, "eval_mass_matrix")
+    import ctypes as C  # noqa: PLC0415
+
+    from . import _lib  # noqa: PLC0415
+
+    dm = model.device_model()
+    fresh = H is None
+    H = _device_out(model, H, (t.env_count * t.na, D, D), "H")
+    if body_I_s is not None:
+        body_I_s = _device_out(model, body_I_s, (t.env_count * t.nb, 6, 6), "body_I_s")
+    if fresh and art_sel is not None:
+        H.zero_()
+    art_mask = _device_art_mask(model, art_sel, "eval_mass_matrix")
+    d = state._desc()
+    _lib.check(dm.lib.nt_eval_mass_matrix(C.byref(dm.desc), C.byref(d), H.data_ptr(), None if body_I_s is None else body_I_s.data_ptr(),
+                                          None if art_mask is None else art_mask.data_ptr(), dm.stream()), "nt_eval_mass_matrix")
+    return H
+
+
+def _eval_jm_groups(model, state, which, out, aux, art_sel):
+    """Heterogeneous model: one call per world group; a group's articulations are a slice of the global outputs, padded to the
+    maxima over the groups (L, D)."""
+    groups = model.world_groups
+    parts = groups.parts
+    L, D = _art_dims(model)
+    A = int(model.articulation_count)
+    gpu = getattr(model, "is_gpu", False)
+    shape = (A, 6 * L, D) if which == "jacobian" else (A, D, D)
+    aux_key, aux_shape = (("joint_dof_count", (int(model.joint_dof_count), 6)) if which == "jacobian"
+                          else ("body_count", (int(model.body_count), 6, 6)))
+    if not gpu:
+        fn = eval_jacobian_numpy if which == "jacobian" else eval_mass_matrix_numpy
+        return fn(model, _host_array(state.body_q), _host_array(state.joint_q), out, aux, art_sel)
+    import torch  # noqa: PLC0415
+
+    dev = parts[0].device_model().device
+    if out is None:
+        out = torch.zeros(shape, dtype=torch.float32, device=dev)
+    elif not (hasattr(out, "data_ptr") and out.dtype == torch.float32 and tuple(out.shape) == shape):
+        raise ValueError(f"the output must be a float32 tensor of shape {shape}")
+    if aux is not None and not (hasattr(aux, "data_ptr") and aux.dtype == torch.float32 and tuple(aux.shape) == aux_shape):
+        raise ValueError(f"the optional output must be a float32 tensor of shape {aux_shape}")
+    a_edges = np.concatenate([[0], np.cumsum([p.articulation_count for p in parts])])
+    x_edges = np.concatenate([[0], np.cumsum([getattr(p, aux_key) for p in parts])])
+    call = eval_jacobian if which == "jacobian" else eval_mass_matrix
+
+    def go(i, p):
+        if not p.articulation_count:
+            return
+        a0, a1 = int(a_edges[i]), int(a_edges[i + 1])
+        sel = None if art_sel is None else art_sel[a0:a1]
+        Lp, Dp = _art_dims(p)
+        xs = None if aux is None else aux[int(x_edges[i]):int(x_edges[i + 1])]
+        same = (Lp, Dp) == (L, D) if which == "jacobian" else Dp == D
+        if same:  # the group's slice has the global shape: written in place
+            call(p, state.parts[i], out[a0:a1], xs, mask=sel) if which == "jacobian" else call(p, state.parts[i], out[a0:a1],
+                                                                                                 body_I_s=xs, mask=sel)
+            return
+        got = call(p, state.parts[i], None, xs, mask=sel) if which == "jacobian" else call(p, state.parts[i], None, body_I_s=xs, mask=sel)
+        rows = torch.arange(a0, a1, device=dev) if sel is None else torch.as_tensor(a0 + np.flatnonzero(sel), device=dev)
+        pick = slice(None) if sel is None else torch.as_tensor(np.flatnonzero(sel), device=dev)
+        out[rows] = 0.0
+        if which == "jacobian":
+            out[rows, :6 * Lp, :Dp] = got[pick]
+        else:
+            out[rows, :Dp, :Dp] = got[pick]
+
+    groups.run(go)
+    return out

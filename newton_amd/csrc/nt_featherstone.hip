@@ -1,7 +1,7 @@
 // nt_featherstone.hip -- SolverFeatherstone (step / fused rollout), eval_fk and eval_ik: launch code + C ABI.  The solver's kernels are
 // nt_featherstone_kernels.hpp, their phases nt_featherstone.hpp (namespace ieee); this unit exists so that they are compiled with the
-// default scheduler (see nt_step_preamble.hpp).  eval_ik (kernel and entry points, include/newton_hip_kinematics.h) lives here whole:
-// the headers the stepping unit shares stay as they are.
+// default scheduler (see nt_step_preamble.hpp).  eval_ik, eval_jacobian and eval_mass_matrix (kernels and entry points,
+// include/newton_hip_kinematics.h) live here whole: the headers the stepping unit shares stay as they are.
 #include "nt_step_preamble.hpp"
 #ifndef NT_EMULATED_GRID
 #include "../../include/newton_hip_kinematics.h"
@@ -168,6 +168,341 @@ __global__ void __launch_bounds__(256) eval_ik_kernel(KArgs a, float* joint_q, f
         const int d0 = c.T.joint_qd_start[j0], d1 = j1 < m.nj ? c.T.joint_qd_start[j1] : m.nd;
         unstage_rows(c, oq + q0, joint_q + (size_t)q0 * c.ES, q1 - q0);
         unstage_rows(c, oqd + d0, joint_qd + (size_t)d0 * c.ES, d1 - d0);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// newton.eval_jacobian / eval_mass_matrix (newton/_src/sim/articulation.py; contract: include/newton_hip_kinematics.h).  Both kernels
+// build the motion-subspace column S_d of every (environment, dof) from the parent pose in body_q and the joint's own joint_q -- eval_fk's
+// composition -- and keep it in LDS.  Tile: the persistent block of the XPBD layout without its body-derived tile, then joint_q [nc],
+// S (ENV-MAJOR: [e][6][nd], odd stride -- the streaming phase reads it with consecutive lanes on consecutive dofs), and for the mass
+// matrix the composite inertias [10][nj] and H (env-major [e][nd][D]).  Block-shared ints behind the topology: the joint's ancestor
+// joint, depth and articulation, the joint of each dof, and per joint the bit mask of the joints on its root path (itself included).
+// ------------------------------------------------------------------------------------------------
+struct JmLayout {
+    int jq, S, SW, Ic, H, HW, rows;
+};
+__host__ __device__ inline JmLayout jm_layout(const nt_model& m, const bool uni, const bool mass) {
+    JmLayout F;
+    int o = make_layout(m, false, false, uni, false).bd.off;
+    F.jq = o; o += m.nc;
+    F.SW = (6 * m.nd) | 1;
+    F.S = o; o += F.SW;
+    F.Ic = o; o += mass ? 10 * m.nj : 0;
+    F.HW = (m.nd * m.max_art_dofs) | 1;
+    F.H = o; o += mass ? F.HW : 0;
+    F.rows = o;
+    return F;
+}
+__host__ __device__ inline int jm_table_ints(const nt_model& m) { return 3 * m.nj + m.nd + m.nj * fs_mask_words(m); }
+
+template <int EPB>
+struct JmCtx {
+    const Ctx<EPB>& c;
+    JmLayout F;
+    const int *anc, *depth, *art, *dof_joint;
+    const unsigned* pathmask;
+    int words;
+    static constexpr int N = Ctx<EPB>::N;
+    NT_DI JmCtx(const Ctx<EPB>& c_, const JmLayout& F_, const int* extra) : c(c_), F(F_) {
+        const int nj = c.a.m.nj;
+        anc = extra; depth = extra + nj; art = extra + 2 * nj; dof_joint = extra + 3 * nj;
+        pathmask = reinterpret_cast<const unsigned*>(extra + 3 * nj + c.a.m.nd);
+        words = fs_mask_words(c.a.m);
+    }
+    // is joint `a` on the root path of joint `l` (or `l` itself)?
+    NT_DI bool on_path(int a, int l) const { return (pathmask[l * words + (a >> 5)] >> (a & 31)) & 1u; }
+    NT_DI float& S(int e, int comp, int d) const { return c.lds[F.S * N + e * F.SW + comp * c.a.m.nd + d]; }
+    NT_DI float& H(int e, int i, int lj) const { return c.lds[F.H * N + e * F.HW + i * c.a.m.max_art_dofs + lj]; }
+    NT_DI float& Ic(int comp, int j) const { return c.lds[(F.Ic + comp * c.a.m.nj + j) * N + c.e]; }
+    NT_DI float jq(int i) const { return c.lds[(F.jq + i) * N + c.e]; }
+    NT_DI int qd_end(int j) const { return j + 1 < c.a.m.nj ? c.T.joint_qd_start[j + 1] : c.a.m.nd; }
+    NT_DI int max_depth() const {
+        int d = 0;
+        for (int j = 0; j < c.a.m.nj; ++j) d = imax(d, depth[j]);
+        return d;
+    }
+};
+
+// the tables (every thread of the workgroup; the staged topology must be published: one barrier after Ctx's constructor)
+template <int EPB>
+NT_DI void jm_build_tables(const Ctx<EPB>& c, int* extra) {
+    const nt_model& m = c.a.m;
+    const int nj = m.nj, words = fs_mask_words(m);
+    for (int j = threadIdx.x; j < nj; j += blockDim.x) {
+        int p = c.T.joint_parent[j], anc = -1, art = 0;
+        for (int k = 0; k < m.na; ++k)
+            if (m.art_start[k] <= j) art = k;
+        if (p >= 0)  // the joint of the same articulation whose child is this joint's parent body
+            for (int k = m.art_start[art]; k < m.art_start[art + 1]; ++k)
+                if (c.T.joint_child[k] == p) anc = k;
+        extra[j] = anc;
+        extra[2 * nj + j] = art;
+    }
+    for (int d = threadIdx.x; d < m.nd; d += blockDim.x) {
+        int j = 0;
+        for (int k = 1; k < nj; ++k)
+            if (c.T.joint_qd_start[k] <= d) j = k;
+        extra[3 * nj + d] = j;
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < nj; j += blockDim.x) {
+        int d = 0, k = extra[j];
+        unsigned* mask = reinterpret_cast<unsigned*>(extra + 3 * nj + m.nd) + j * words;
+        for (int w = 0; w < words; ++w) mask[w] = 0u;
+        mask[j >> 5] |= 1u << (j & 31);
+        while (k >= 0 && d < nj) {
+            d += 1;
+            mask[k >> 5] |= 1u << (k & 31);
+            k = extra[k];
+        }
+        extra[nj + j] = d;
+    }
+    __syncthreads();
+}
+
+// S_d of dof d as an origin-referenced world twist (linear, angular) about the point `ref` (the closed forms of the header)
+template <int EPB>
+NT_DI void jm_S_item(const JmCtx<EPB>& f, int d, vec3 ref) {
+    const Ctx<EPB>& c = f.c;
+    const nt_model& m = c.a.m;
+    const int j = f.dof_joint[d];
+    const int parent = c.T.joint_parent[j], child = c.T.joint_child[j], type = c.T.joint_type[j];
+    const int ds = c.T.joint_qd_start[j], cs = c.T.joint_q_start[j], k = d - ds;
+    const int lin = c.T.joint_lin_count[j], ang = c.T.joint_ang_count[j];
+    xform X_wpj = c.plxf(c.L.jp, 0, m.nj, j);
+    if (parent >= 0) X_wpj = c.body_q(parent) * X_wpj;
+    const vec3 unit(k % 3 == 0 ? 1.0f : 0.0f, k % 3 == 1 ? 1.0f : 0.0f, k % 3 == 2 ? 1.0f : 0.0f);
+    vec3 a_lin, a_ang, pivot = X_wpj.p;  // (axes in the parent anchor frame)
+    bool angular = false;
+    if (type == JT_PRISMATIC) {
+        a_lin = c.dof_axis(d);
+    } else if (type == JT_REVOLUTE) {
+        a_ang = c.dof_axis(d);
+        angular = true;
+    } else if (type == JT_BALL) {
+        a_ang = unit;
+        angular = true;
+    } else if (type == JT_FREE || type == JT_DISTANCE) {
+        if (k < 3) {
+            a_lin = unit;
+        } else {  // about the child's COM: joint_qd's linear part is the COM velocity
+            a_ang = unit;
+            angular = true;
+            pivot = xform_point(c.body_q(child), c.com(child));
+        }
+    } else if (type == JT_D6) {
+        if (k < lin) {
+            a_lin = c.dof_axis(d);
+        } else {
+            angular = true;
+            vec3 pos(0.0f);
+            for (int i = 0; i < lin; ++i) pos += c.dof_axis(ds + i) * f.jq(cs + i);
+            pivot = xform_point(X_wpj, pos);
+            if (ang == 1) {
+                a_ang = c.dof_axis(d);
+            } else {
+                vec3 a0, a1, a2;
+                d6_multi_angular(ang, c.dof_axis(ds + lin), c.dof_axis(ds + lin + 1), ang == 3 ? c.dof_axis(ds + lin + 2) : vec3(),
+                                 f.jq(cs + lin), f.jq(cs + lin + 1), ang == 3 ? f.jq(cs + lin + 2) : 0.0f, a0, a1, a2);
+                a_ang = k - lin == 0 ? a0 : (k - lin == 1 ? a1 : a2);
+            }
+        }
+    }
+    vec3 top, bottom;
+    if (angular) {
+        bottom = quat_rotate(X_wpj.q, a_ang);
+        top = cross(pivot - ref, bottom);
+    } else {
+        top = quat_rotate(X_wpj.q, a_lin);
+    }
+    f.S(c.e, 0, d) = top.x; f.S(c.e, 1, d) = top.y; f.S(c.e, 2, d) = top.z;
+    f.S(c.e, 3, d) = bottom.x; f.S(c.e, 4, d) = bottom.y; f.S(c.e, 5, d) = bottom.z;
+}
+
+// the widest articulation in joints (the row blocks of J)
+NT_DI int jm_max_joints(const nt_model& m) {
+    int L = 0;
+    for (int k = 0; k < m.na; ++k) L = imax(L, m.art_start[k + 1] - m.art_start[k]);
+    return L;
+}
+
+// staging shared by both kernels: body poses, parameters, joint_q
+template <int EPB>
+NT_DI void jm_load(const Ctx<EPB>& c, const JmLayout& F) {
+    const nt_model& m = c.a.m;
+    if (c.valid) stage_rows(c, c.L.bq, c.a.s_in.body_q, 7, m.nb);
+    load_params(c, false);
+    if (c.valid) stage_rows(c, F.jq, c.a.s_in.joint_q, m.nc);
+}
+
+// J [env_count * na][6 L][D] and (optional) joint_S_s [env_count * nd][6], both in the public layout.  art_mask as for eval_ik_kernel.
+template <int EPB>
+__global__ void __launch_bounds__(256) eval_jacobian_kernel(KArgs a, float* J, float* joint_S_s, const uint8_t* art_mask) {
+    extern __shared__ __align__(16) float lds[];
+    const nt_model& m = a.m;
+    constexpr int N = Ctx<EPB>::N;
+    const JmLayout F = jm_layout(m, Ctx<EPB>::UNI, false);
+    Ctx<EPB> c(a, lds, F.rows);
+    int* extra = reinterpret_cast<int*>(lds + (size_t)F.rows * N) + topo_ints(m);
+    c.up = reinterpret_cast<float*>(extra + jm_table_ints(m));
+    __syncthreads();
+    jm_build_tables(c, extra);
+    const JmCtx<EPB> f(c, F, extra);
+    jm_load(c, F);
+    __syncthreads();
+    if (c.valid)
+        for (int d = c.slot; d < m.nd; d += c.nslot)
+            if (!art_mask || art_mask[(size_t)c.env * m.na + f.art[f.dof_joint[d]]]) jm_S_item(f, d, vec3());
+    __syncthreads();
+    // stream the tile's articulations: lanes over the flattened [6 L][D] block, zeros from the ancestor test
+    const int L = jm_max_joints(m), D = m.max_art_dofs, block = 6 * L * D;
+    for (int t = 0; t < N * m.na; ++t) {
+        const int e = t / m.na, k = t - e * m.na, env = blockIdx.x * N + e;
+        if (env >= m.env_count) break;
+        if (art_mask && !art_mask[(size_t)env * m.na + k]) continue;
+        const int j0 = m.art_start[k], nja = m.art_start[k + 1] - j0;
+        const int d0 = nja > 0 ? c.T.joint_qd_start[j0] : 0, nda = nja > 0 ? f.qd_end(j0 + nja - 1) - d0 : 0;
+        float* out = J + (size_t)((size_t)env * m.na + k) * block;
+        for (int i = threadIdx.x; i < block; i += blockDim.x) {
+            const int row = i / D, col = i - row * D, jl = row / 6, comp = row - jl * 6;
+            float v = 0.0f;
+            if (jl < nja && col < nda && f.on_path(f.dof_joint[d0 + col], j0 + jl)) v = f.S(e, comp, d0 + col);
+            out[i] = v;
+        }
+    }
+    if (!joint_S_s) return;
+    for (int e = 0; e < N; ++e) {
+        const int env = blockIdx.x * N + e;
+        if (env >= m.env_count) break;
+        float* out = joint_S_s + (size_t)env * m.nd * 6;
+        for (int i = threadIdx.x; i < 6 * m.nd; i += blockDim.x) {
+            const int d = i / 6, comp = i - d * 6;
+            if (!art_mask || art_mask[(size_t)env * m.na + f.art[f.dof_joint[d]]]) out[i] = f.S(e, comp, d);
+        }
+    }
+}
+
+// link j's spatial inertia about `ref` as {mass, first moment h = m c, rotational inertia about ref (xx xy xz yy yz zz)}: ten numbers
+// that add under composition.  body_I_s (optional): the dense 6 x 6 about the world origin, [env * nb + body][6][6].
+template <int EPB>
+NT_DI void jm_inertia_item(const JmCtx<EPB>& f, int j, vec3 ref, float* body_I_s) {
+    const Ctx<EPB>& c = f.c;
+    const nt_model& m = c.a.m;
+    const int b = c.T.joint_child[j];
+    const xform X = c.body_q(b);
+    const float mass = c.pl(c.L.bp, BP_MASS, m.nb, b);
+    const mat33 R = quat_to_matrix(X.q);
+    const mat33 Ib = c.inertia(b);
+    const vec3 r0(R.m00, R.m01, R.m02), r1(R.m10, R.m11, R.m12), r2(R.m20, R.m21, R.m22);
+    const vec3 t0 = Ib * r0, t1 = Ib * r1, t2 = Ib * r2;  // R I R^T, entry (i, j) = r_i . (I r_j)
+    const float wxx = dot(r0, t0), wxy = dot(r0, t1), wxz = dot(r0, t2), wyy = dot(r1, t1), wyz = dot(r1, t2), wzz = dot(r2, t2);
+    const vec3 cw = xform_point(X, c.com(b));
+    auto rotational = [&](vec3 r, float (&o)[6]) {  // R I R^T - m [r]x [r]x
+        o[0] = wxx + mass * (r.y * r.y + r.z * r.z); o[1] = wxy - mass * (r.x * r.y); o[2] = wxz - mass * (r.x * r.z);
+        o[3] = wyy + mass * (r.x * r.x + r.z * r.z); o[4] = wyz - mass * (r.y * r.z); o[5] = wzz + mass * (r.x * r.x + r.y * r.y);
+    };
+    const vec3 r = cw - ref;
+    float io[6];
+    rotational(r, io);
+    f.Ic(0, j) = mass;
+    f.Ic(1, j) = mass * r.x; f.Ic(2, j) = mass * r.y; f.Ic(3, j) = mass * r.z;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) f.Ic(4 + k, j) = io[k];
+    if (body_I_s) {
+        rotational(cw, io);
+        const vec3 h = cw * mass;
+        const float M[6][6] = {{mass, 0.0f, 0.0f, 0.0f, h.z, -h.y},  {0.0f, mass, 0.0f, -h.z, 0.0f, h.x},  {0.0f, 0.0f, mass, h.y, -h.x, 0.0f},
+                               {0.0f, -h.z, h.y, io[0], io[1], io[2]}, {h.z, 0.0f, -h.x, io[1], io[3], io[4]}, {-h.y, h.x, 0.0f, io[2], io[4], io[5]}};
+        float* out = body_I_s + ((size_t)c.env * m.nb + b) * 36;
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int k = 0; k < 6; ++k) out[i * 6 + k] = M[i][k];
+    }
+}
+
+// H [env_count * na][D][D] and (optional) body_I_s.  Twists and inertias are referenced to the position of the articulation's root
+// link (H does not depend on the point; world coordinates of a far-away world would cost the m |c|^2 terms their digits).
+template <int EPB>
+__global__ void __launch_bounds__(256) eval_mass_matrix_kernel(KArgs a, float* H, float* body_I_s, const uint8_t* art_mask) {
+    extern __shared__ __align__(16) float lds[];
+    const nt_model& m = a.m;
+    constexpr int N = Ctx<EPB>::N;
+    const JmLayout F = jm_layout(m, Ctx<EPB>::UNI, true);
+    Ctx<EPB> c(a, lds, F.rows);
+    int* extra = reinterpret_cast<int*>(lds + (size_t)F.rows * N) + topo_ints(m);
+    c.up = reinterpret_cast<float*>(extra + jm_table_ints(m));
+    __syncthreads();
+    jm_build_tables(c, extra);
+    const JmCtx<EPB> f(c, F, extra);
+    const int max_depth = f.max_depth(), D = m.max_art_dofs;
+    jm_load(c, F);
+    __syncthreads();
+    auto selected = [&](int j) { return !art_mask || art_mask[(size_t)c.env * m.na + f.art[j]]; };
+    auto root_pos = [&](int j) { return c.body_q(c.T.joint_child[m.art_start[f.art[j]]]).p; };
+    if (c.valid) {
+        for (int d = c.slot; d < m.nd; d += c.nslot)
+            if (selected(f.dof_joint[d])) jm_S_item(f, d, root_pos(f.dof_joint[d]));
+        for (int j = c.slot; j < m.nj; j += c.nslot)
+            if (selected(j)) jm_inertia_item(f, j, root_pos(j), body_I_s);
+    }
+    __syncthreads();
+    // composite inertias up the tree: a joint adds its children's (complete since the previous interval) in ascending joint order
+    for (int lvl = max_depth - 1; lvl >= 0; --lvl) {
+        if (c.valid)
+            for (int j = c.slot; j < m.nj; j += c.nslot) {
+                if (f.depth[j] != lvl || !selected(j)) continue;
+                float acc[10];
+#pragma unroll
+                for (int k = 0; k < 10; ++k) acc[k] = f.Ic(k, j);
+                for (int ch = m.art_start[f.art[j]]; ch < m.art_start[f.art[j] + 1]; ++ch) {
+                    if (f.anc[ch] != j) continue;
+#pragma unroll
+                    for (int k = 0; k < 10; ++k) acc[k] += f.Ic(k, ch);
+                }
+#pragma unroll
+                for (int k = 0; k < 10; ++k) f.Ic(k, j) = acc[k];
+            }
+        __syncthreads();
+    }
+    // H_ij = S_i . (I^c_deeper S_j) for ancestor-related dofs i >= j of one articulation, both triangles from one lane
+    if (c.valid)
+        for (int item = c.slot; item < m.nd * D; item += c.nslot) {
+            const int i = item / D, lj = item - i * D, ji = f.dof_joint[i];
+            if (!selected(ji)) continue;
+            const int d0 = c.T.joint_qd_start[m.art_start[f.art[ji]]], j = d0 + lj;
+            if (j > i) continue;
+            const int jj = f.dof_joint[j];
+            const int deep = f.on_path(jj, ji) ? ji : (f.on_path(ji, jj) ? jj : -1);
+            float h = 0.0f;
+            if (deep >= 0) {
+                const vec3 vi(f.S(c.e, 0, i), f.S(c.e, 1, i), f.S(c.e, 2, i)), wi(f.S(c.e, 3, i), f.S(c.e, 4, i), f.S(c.e, 5, i));
+                const vec3 vj(f.S(c.e, 0, j), f.S(c.e, 1, j), f.S(c.e, 2, j)), wj(f.S(c.e, 3, j), f.S(c.e, 4, j), f.S(c.e, 5, j));
+                const float mass = f.Ic(0, deep);
+                const vec3 hm(f.Ic(1, deep), f.Ic(2, deep), f.Ic(3, deep));
+                const float xx = f.Ic(4, deep), xy = f.Ic(5, deep), xz = f.Ic(6, deep), yy = f.Ic(7, deep), yz = f.Ic(8, deep), zz = f.Ic(9, deep);
+                const vec3 top = vj * mass + cross(wj, hm);
+                const vec3 bottom = cross(hm, vj) + vec3(xx * wj.x + xy * wj.y + xz * wj.z, xy * wj.x + yy * wj.y + yz * wj.z,
+                                                        xz * wj.x + yz * wj.y + zz * wj.z);
+                h = dot(vi, top) + dot(wi, bottom);
+            }
+            f.H(c.e, i, lj) = h;
+            f.H(c.e, j, i - d0) = h;
+        }
+    __syncthreads();
+    const int block = D * D;
+    for (int t = 0; t < N * m.na; ++t) {
+        const int e = t / m.na, k = t - e * m.na, env = blockIdx.x * N + e;
+        if (env >= m.env_count) break;
+        if (art_mask && !art_mask[(size_t)env * m.na + k]) continue;
+        const int j0 = m.art_start[k], nja = m.art_start[k + 1] - j0;
+        const int d0 = nja > 0 ? c.T.joint_qd_start[j0] : 0, nda = nja > 0 ? f.qd_end(j0 + nja - 1) - d0 : 0;
+        float* out = H + (size_t)((size_t)env * m.na + k) * block;
+        for (int i = threadIdx.x; i < block; i += blockDim.x) {
+            const int li = i / D, lj = i - li * D;
+            out[i] = li < nda && lj < nda ? f.H(e, d0 + li, lj) : 0.0f;
+        }
     }
 }
 
@@ -340,6 +675,72 @@ nt_status nt_eval_ik_tile(const nt_model* m, const nt_state* in, float* joint_q,
 
 nt_status nt_eval_ik(const nt_model* m, const nt_state* in, float* joint_q, float* joint_qd, const uint8_t* art_mask, void* stream) {
     return nt_eval_ik_tile(m, in, joint_q, joint_qd, art_mask, 0, stream);
+}
+
+}  // extern "C"
+
+// shared launch code of nt_eval_jacobian_tile / nt_eval_mass_matrix_tile (tile rule: nt_eval_ik_tile's)
+template <bool MASS>
+static nt_status jm_launch(const nt_model* m, const nt_state* in, float* out, float* aux, const uint8_t* art_mask, int32_t envs_per_block,
+                           hipStream_t stream) {
+    if (!model_ok(m) || !in || !in->body_q || !in->joint_q || !out) return NT_ERR_INVALID_ARG;
+    if (m->nj <= 0 || m->na <= 0 || !m->art_start || m->max_art_dofs < 0) return NT_ERR_UNSUPPORTED;
+#ifdef NT_DEV_FAST
+    return NT_ERR_UNSUPPORTED;
+#else
+    if (m->max_art_dofs == 0) return NT_OK;  // (no dofs: J and H have no entries)
+    KArgs a = {};
+    a.m = *m;
+    a.s_in = *in;
+    const size_t shared_ints = (size_t)topo_ints(*m) + jm_table_ints(*m);
+    auto bytes = [&](int epb, bool uni) {
+        return tile_bytes(jm_layout(*m, uni, MASS).rows, epb, shared_ints, uni ? make_layout(*m, false, false, true, false).uni_floats : 0);
+    };
+    const bool uni = envs_per_block == 0 && m->params_uniform && bytes(16, true) <= LDS_BYTES_PER_CU;
+    int epb = 0;
+    if (uni) {
+        epb = 16;
+    } else if (envs_per_block == 0) {
+        const int cands[4] = {16, 8, 4, 1};
+        for (int i = 0; i < 4 && !epb; ++i)
+            if (bytes(cands[i], false) <= LDS_BYTES_PER_CU) epb = cands[i];
+    } else if ((envs_per_block == 1 || envs_per_block == 4 || envs_per_block == 8 || envs_per_block == 16) &&
+               bytes(envs_per_block, false) <= LDS_BYTES_PER_CU) {
+        epb = envs_per_block;
+    }
+    if (!epb) return NT_ERR_UNSUPPORTED;
+    // slot-lanes: one per dof / joint / body (mass matrix: per entry of a dof's H row block); the streaming phase runs workgroup-wide
+    const int want = imax(imax(m->nb, m->nj), MASS ? m->nd * m->max_art_dofs : m->nd), cap = 256 / epb;
+    a.nslot = want < cap ? want : cap;
+    if (uni) {
+        if constexpr (MASS) return launch_tile(eval_mass_matrix_kernel<16 + NT_UNI>, a, 16, bytes(16, true), stream, out, aux, art_mask);
+        else return launch_tile(eval_jacobian_kernel<16 + NT_UNI>, a, 16, bytes(16, true), stream, out, aux, art_mask);
+    }
+    return dispatch_epb(Epbs<16, 8, 4, 1>{}, epb, [&](auto E) {
+        if constexpr (MASS) return launch_tile(eval_mass_matrix_kernel<E>, a, E, bytes(E, false), stream, out, aux, art_mask);
+        else return launch_tile(eval_jacobian_kernel<E>, a, E, bytes(E, false), stream, out, aux, art_mask);
+    });
+#endif
+}
+
+extern "C" {
+
+nt_status nt_eval_jacobian_tile(const nt_model* m, const nt_state* in, float* J, float* joint_S_s, const uint8_t* art_mask,
+                                int32_t envs_per_block, void* stream) {
+    return jm_launch<false>(m, in, J, joint_S_s, art_mask, envs_per_block, (hipStream_t)stream);
+}
+
+nt_status nt_eval_jacobian(const nt_model* m, const nt_state* in, float* J, float* joint_S_s, const uint8_t* art_mask, void* stream) {
+    return nt_eval_jacobian_tile(m, in, J, joint_S_s, art_mask, 0, stream);
+}
+
+nt_status nt_eval_mass_matrix_tile(const nt_model* m, const nt_state* in, float* H, float* body_I_s, const uint8_t* art_mask,
+                                   int32_t envs_per_block, void* stream) {
+    return jm_launch<true>(m, in, H, body_I_s, art_mask, envs_per_block, (hipStream_t)stream);
+}
+
+nt_status nt_eval_mass_matrix(const nt_model* m, const nt_state* in, float* H, float* body_I_s, const uint8_t* art_mask, void* stream) {
+    return nt_eval_mass_matrix_tile(m, in, H, body_I_s, art_mask, 0, stream);
 }
 
 #ifdef NT_PHASE_TIMING

@@ -698,6 +698,23 @@ class Model:
     def is_gpu(self):
         return _is_gpu(self.device)
 
+    def _articulation_widths(self):
+        """(joints, dofs) of the widest articulation: the padded block shape of eval_jacobian / eval_mass_matrix."""
+        A = int(getattr(self, "articulation_count", 0))
+        if not A:
+            return 0, 0
+        starts, ends = np.asarray(self.articulation_start, dtype=np.int64), np.asarray(self.articulation_end, dtype=np.int64)
+        dof_edges = np.concatenate([np.asarray(self.joint_qd_start, dtype=np.int64), [int(self.joint_dof_count)]])
+        return int((ends - starts).max()), int((dof_edges[ends] - dof_edges[starts]).max())
+
+    @property
+    def max_joints_per_articulation(self) -> int:
+        return self._articulation_widths()[0]
+
+    @property
+    def max_dofs_per_articulation(self) -> int:
+        return self._articulation_widths()[1]
+
     def device_model(self) -> DeviceModel:
         if not self.is_gpu:
             raise _lib.NewtonHipError(

@@ -1,6 +1,6 @@
 """ArticulationView -- the subset of newton.selection.ArticulationView (newton/_src/utils/selection.py:500-1800) that an RL
 loop calls between steps: per-world getters / setters for root pose and twist, dof positions / velocities / forces and
-link poses, with an optional world mask, plus masked eval_fk / eval_ik.
+link poses, with an optional world mask, plus masked eval_fk / eval_ik / eval_jacobian / eval_mass_matrix.
 
 With the env-major SoA layout these are not gather/scatter kernels: ``State._soa[name]`` has shape
 ``[comp, slots_per_env, env_stride]``, so "the dofs of every world" is a strided *view* ``soa[0, a:b, :E].T`` (no copy on
@@ -13,7 +13,7 @@ import fnmatch
 
 import numpy as np
 
-from ..articulation import eval_fk, eval_ik
+from ..articulation import eval_fk, eval_ik, eval_jacobian, eval_mass_matrix
 from ..enums import JointType
 
 
@@ -197,3 +197,25 @@ class ArticulationView:
         probe = state._soa["joint_q"] if getattr(self.model, "is_gpu", False) and hasattr(state, "_soa") else np.empty(0)
         m = self._mask(mask, probe)
         eval_ik(self.model, state, mask=m.repeat_interleave(na) if hasattr(m, "repeat_interleave") else np.repeat(m, na))
+
+    def _art_mask(self, state, mask):
+        """World mask -> bool per articulation (None: every world)."""
+        if mask is None:
+            return None
+        na = self.model.env.na
+        probe = state._soa["joint_q"] if getattr(self.model, "is_gpu", False) and hasattr(state, "_soa") else np.empty(0)
+        m = self._mask(mask, probe)
+        return m.repeat_interleave(na) if hasattr(m, "repeat_interleave") else np.repeat(m, na)
+
+    def _art_slice(self, out):
+        """[world, ...] slice of the view's articulation in a [articulation_count, ...] output."""
+        return out.reshape(self.world_count, self.model.env.na, *out.shape[1:])[:, self.articulation]
+
+    def eval_jacobian(self, state, J=None, mask=None):
+        """newton.eval_jacobian restricted to the selected worlds (the slices of unselected worlds in ``J`` are left untouched); returns
+        the [world, 6 L, D] slice of this view's articulation.  After a maximal-coordinate step call :meth:`eval_ik` first."""
+        return self._art_slice(eval_jacobian(self.model, state, J, mask=self._art_mask(state, mask)))
+
+    def eval_mass_matrix(self, state, H=None, mask=None):
+        """newton.eval_mass_matrix restricted to the selected worlds; returns the [world, D, D] slice of this view's articulation."""
+        return self._art_slice(eval_mass_matrix(self.model, state, H, mask=self._art_mask(state, mask)))
