@@ -100,6 +100,64 @@ nt_status nt_eval_mass_matrix(const nt_model* m, const nt_state* in, float* H, f
 nt_status nt_eval_mass_matrix_tile(const nt_model* m, const nt_state* in, float* H, float* body_I_s, const uint8_t* art_mask,
                                    int32_t envs_per_block, void* stream);
 
+/* Batched inverse kinematics (the capability of the reference's newton.ik.IKSolver: position / rotation / joint-limit objectives,
+ * Levenberg-Marquardt):
+ *   nt_ik_solve           <- newton.ik.IKSolver.step(joint_q_in, joint_q_out, iterations, step_size)     newton/_src/sim/ik/
+ * One problem is one world of the replicated model (the reference takes n_problems beside a single-articulation model).  The variables
+ * are all nd dofs of the world.  All `iterations` run inside ONE launch; between the iterations nothing is read from or written to
+ * device memory.  Everything below is per problem; (p, q) is a link's world pose from nt_eval_fk's composition at the current joint_q.
+ *
+ * Residuals r, stacked in objective order (weight w):
+ *   NT_IK_POSITION     w (p + rot(q, offset.xyz) - target)                                   3 rows, target [env_count][3]
+ *   NT_IK_ROTATION     w 2 vec(q_err), q_err = (q * offset) * conj(target); with NT_IK_CANONICALIZE q_err is negated when its
+ *                      w < 0                                                                 3 rows, target [env_count][4] (xyzw)
+ *   NT_IK_JOINT_LIMIT  one row per dof d of a PRISMATIC / REVOLUTE / D6 joint with lower < upper, both of magnitude below 1e10:
+ *                      w (max(0, q_d - upper) - max(0, lower - q_d))                         target [env_count][2 nd] (lower, upper)
+ *   cost C = |r|^2 / 2.
+ * Jacobian rows, from nt_eval_jacobian's columns (v, omega) of the link (zero off its root path):
+ *   position  w (v + omega x (p + rot(q, offset)))     rotation  w omega (the Gauss-Newton approximation: exact at zero rotation error)
+ *   limit     w on the dof's own column while violated, else 0.
+ * Retraction joint_q (+) delta, consistent with those columns to first order: PRISMATIC / REVOLUTE / D6 coordinates add delta;
+ * BALL q_j <- normalize(exp(delta) q_j) (delta in the parent anchor frame); FREE / DISTANCE: in the parent anchor frame the child's
+ * COM translates by delta_lin and the child rotates by exp(delta_ang) about its COM, joint_q becomes what nt_eval_ik returns for that
+ * pose.  exp(d) = (d sin(|d| / 2) / |d|, cos(|d| / 2)), (d / 2, 1) for d = 0.
+ * One iteration: A = J^T J + lambda I, g = J^T r, A delta = -g by Cholesky, q' = q (+) s delta (s = step_size), C' = C(q'),
+ *   pred = s (s lambda delta.delta - (2 - s) g.delta) / 2     (the reduction of the quadratic model for the scaled step;
+ *                                                               s = 1: delta . (lambda delta - g) / 2)
+ *   rho = (C - C') / pred.  Accepted when pred > 0, C' < C and rho > rho_min: q <- q', lambda <- max(lambda / lambda_factor,
+ *   lambda_min); otherwise q stays bit for bit and lambda <- min(lambda lambda_factor, lambda_max).  A non-positive pivot is a rejection.
+ * joint_q_in / joint_q_out: the PUBLIC layout [env_count][nc] (not environment-major); they may be the same array.  lambda
+ * [env_count] is read and written (it persists across calls), cost [env_count] receives the cost at joint_q_out.  iterations = 0
+ * copies joint_q and evaluates cost.  The targets are read through the pointers at launch time: an in-place update followed by a
+ * graph replay takes effect.  Needs worlds whose bodies are all some joint's child and whose joints all belong to articulations;
+ * multi-axis D6 joints as for nt_eval_ik (the caller vouches).  IEEE arithmetic in a fixed order: every tile gives the same bits,
+ * identical worlds give identical rows.  Errors: null pointers, iterations < 0 NT_ERR_INVALID_ARG; more than NT_IK_MAX_OBJECTIVES
+ * objectives, an unknown objective type, a link outside 0 .. nb - 1, nj <= 0, na <= 0, nd <= 0, a tile that does not fit the CU's LDS,
+ * an envs_per_block other than 0 / 1 / 4 / 8 / 16, a build with NT_DEV_FAST: NT_ERR_UNSUPPORTED.  No allocation, no synchronisation;
+ * recordable by nt_graph_capture_begin / _end. */
+#define NT_IK_MAX_OBJECTIVES 8
+enum { NT_IK_POSITION = 0, NT_IK_ROTATION = 1, NT_IK_JOINT_LIMIT = 2 };
+enum { NT_IK_CANONICALIZE = 1 };
+typedef struct nt_ik_objective {
+    int32_t type;        /* NT_IK_POSITION / _ROTATION / _JOINT_LIMIT */
+    int32_t link;        /* world-local body index (position, rotation) */
+    int32_t flags;       /* NT_IK_CANONICALIZE (rotation) */
+    float weight;
+    float offset[4];     /* position: the point in the link frame (xyz); rotation: the offset rotation (xyzw) */
+    const float* target; /* device pointer, layout by type (above) */
+} nt_ik_objective;
+typedef struct nt_ik_problem {
+    int32_t count;
+    float lambda_factor, lambda_min, lambda_max, rho_min;
+    nt_ik_objective obj[NT_IK_MAX_OBJECTIVES];
+} nt_ik_problem;
+
+nt_status nt_ik_solve(const nt_model* m, const nt_ik_problem* p, const float* joint_q_in, float* joint_q_out, float* lambda, float* cost,
+                      int32_t iterations, float step_size, void* stream);
+/* the tile named as for nt_eval_ik_tile */
+nt_status nt_ik_solve_tile(const nt_model* m, const nt_ik_problem* p, const float* joint_q_in, float* joint_q_out, float* lambda, float* cost,
+                           int32_t iterations, float step_size, int32_t envs_per_block, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,6 +55,21 @@ class nt_state(C.Structure):
                 ("joint_qd", C.c_void_p), ("body_parent_f", C.c_void_p)]
 
 
+NT_IK_MAX_OBJECTIVES = 8
+NT_IK_POSITION, NT_IK_ROTATION, NT_IK_JOINT_LIMIT = 0, 1, 2
+NT_IK_CANONICALIZE = 1
+
+
+class nt_ik_objective(C.Structure):  # include/newton_hip_kinematics.h
+    _fields_ = [("type", C.c_int32), ("link", C.c_int32), ("flags", C.c_int32), ("weight", C.c_float), ("offset", C.c_float * 4),
+                ("target", C.c_void_p)]
+
+
+class nt_ik_problem(C.Structure):
+    _fields_ = [("count", C.c_int32), ("lambda_factor", C.c_float), ("lambda_min", C.c_float), ("lambda_max", C.c_float),
+                ("rho_min", C.c_float), ("obj", nt_ik_objective * NT_IK_MAX_OBJECTIVES)]
+
+
 class nt_control(C.Structure):
     _fields_ = [("joint_f", C.c_void_p), ("joint_target_q", C.c_void_p), ("joint_target_qd", C.c_void_p)]
 
@@ -437,6 +452,8 @@ SYMBOLS = {
     "nt_eval_jacobian_tile": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_state), _P, _P, _P, C.c_int32, _P]),
     "nt_eval_mass_matrix": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_state), _P, _P, _P, _P]),
     "nt_eval_mass_matrix_tile": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_state), _P, _P, _P, C.c_int32, _P]),
+    "nt_ik_solve": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_ik_problem), _P, _P, _P, _P, C.c_int32, C.c_float, _P]),
+    "nt_ik_solve_tile": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_ik_problem), _P, _P, _P, _P, C.c_int32, C.c_float, C.c_int32, _P]),
     "nt_hydro_collide": (C.c_int32, [C.POINTER(nt_hydro_args), _P]),
     "nt_hydro_pairs": (C.c_int32, [C.POINTER(nt_hydro_args), _P]),
     "nt_sdf_candidate_pairs": (C.c_int32, [C.POINTER(nt_sdf_scene), _P, _P, _P, _P, _P, _P]),

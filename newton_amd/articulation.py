@@ -77,6 +77,12 @@ def eval_fk_numpy(model, joint_q, joint_qd):
         jqd = np.split(np.asarray(joint_qd, dtype=np.float32), np.cumsum([p.joint_dof_count for p in parts])[:-1])
         res = [eval_fk_numpy(p, a, b) for p, a, b in zip(parts, jq, jqd)]
         return np.concatenate([r[0] for r in res]), np.concatenate([r[1] for r in res])
+    body_q, body_qd = _eval_fk_float64(model, joint_q, joint_qd)
+    return body_q.reshape(-1, 7).astype(np.float32), body_qd.reshape(-1, 6).astype(np.float32)
+
+
+def _eval_fk_float64(model, joint_q, joint_qd):
+    """eval_fk_numpy before the rounding: (body_q [E, nb, 7], body_qd [E, nb, 6]) in float64 (homogeneous models)."""
     t = model.env
     E, nb, nj = t.env_count, t.nb, t.nj
     jq = np.asarray(joint_q, dtype=np.float64).reshape(E, t.nc)
@@ -179,7 +185,7 @@ def eval_fk_numpy(model, joint_q, joint_qd):
         body_q[:, child] = X_wc
         body_qd[:, child, :3] = np.cross(w_o, com_w) + v_o
         body_qd[:, child, 3:] = w_o
-    return body_q.reshape(-1, 7).astype(np.float32), body_qd.reshape(-1, 6).astype(np.float32)
+    return body_q, body_qd
 
 
 def _host_array(x):

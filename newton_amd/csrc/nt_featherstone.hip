@@ -506,6 +506,378 @@ __global__ void __launch_bounds__(256) eval_mass_matrix_kernel(KArgs a, float* H
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// nt_ik_solve (newton.ik.IKSolver.step; contract: include/newton_hip_kinematics.h): batched Levenberg-Marquardt IK, one problem per
+// environment, all iterations in one launch.  Tile: eval_jacobian_kernel's (poses, parameters, joint_q, S), then the candidate's
+// joint_q' [nc] and poses [7 nb], the residual blocks of the accepted point and of the candidate (position: residual + world point, 6
+// rows; rotation 3; joint limit nd), the staged targets, the packed lower triangle of J^T J [nd (nd + 1) / 2] (factored in place, the
+// factor's diagonal beside it), g, delta.  Block-shared behind eval_jacobian's tables: the objective table, IKS_WORDS words each.
+// Every entry of A, g, the factor and every residual row is produced by ONE lane in a fixed order, the scalars (cost, predicted
+// reduction, decision, lambda) by every lane of the environment from the same LDS values: no atomics, no broadcast, the same bits for
+// every tile width.  Barriers are workgroup-wide: every loop bound is block-uniform.
+// ------------------------------------------------------------------------------------------------
+constexpr int IKS_WORDS = 12;  // type, link, flags, weight, offset[4], the link's joint, first residual row, first target row, spare
+__host__ __device__ inline int iks_res_rows(int type, int nd) { return type == NT_IK_POSITION ? 6 : (type == NT_IK_ROTATION ? 3 : nd); }
+__host__ __device__ inline int iks_tgt_rows(int type, int nd) { return type == NT_IK_POSITION ? 3 : (type == NT_IK_ROTATION ? 4 : 2 * nd); }
+struct IksLayout {
+    JmLayout J;
+    int jq2, bq2, R, R2, T, A, Dg, g, X, nR, nT, nA, rows;
+};
+__host__ __device__ inline IksLayout iks_layout(const nt_model& m, const nt_ik_problem& P, const bool uni) {
+    IksLayout F;
+    F.J = jm_layout(m, uni, false);
+    F.nR = F.nT = 0;
+    for (int k = 0; k < P.count; ++k) {
+        F.nR += iks_res_rows(P.obj[k].type, m.nd);
+        F.nT += iks_tgt_rows(P.obj[k].type, m.nd);
+    }
+    F.nA = m.nd * (m.nd + 1) / 2;
+    int o = F.J.rows;
+    F.jq2 = o; o += m.nc;
+    F.bq2 = o; o += 7 * m.nb;
+    F.R = o; o += F.nR;
+    F.R2 = o; o += F.nR;
+    F.T = o; o += F.nT;
+    F.A = o; o += F.nA;
+    F.Dg = o; o += m.nd;
+    F.g = o; o += m.nd;
+    F.X = o; o += m.nd;
+    F.rows = o;
+    return F;
+}
+__host__ __device__ inline int iks_table_ints(const nt_model& m) { return jm_table_ints(m) + NT_IK_MAX_OBJECTIVES * IKS_WORDS; }
+
+NT_DI quat iks_exp(vec3 d) {
+    const float a = length(d);
+    if (a > 0.0f) {
+        const float h = 0.5f * a, s = sinf(h) / a;
+        return quat(d.x * s, d.y * s, d.z * s, cosf(h));
+    }
+    return quat(0.5f * d.x, 0.5f * d.y, 0.5f * d.z, 1.0f);
+}
+
+template <int EPB>
+struct IksCtx {
+    const JmCtx<EPB>& f;
+    const Ctx<EPB>& c;
+    IksLayout F;
+    const int* tab;
+    int count;
+    static constexpr int N = Ctx<EPB>::N;
+    NT_DI IksCtx(const JmCtx<EPB>& f_, const IksLayout& F_, const int* tab_, int count_) : f(f_), c(f_.c), F(F_), tab(tab_), count(count_) {}
+    NT_DI float& row(int r) const { return c.lds[r * N + c.e]; }
+    NT_DI int type(int k) const { return tab[k * IKS_WORDS]; }
+    NT_DI int link(int k) const { return tab[k * IKS_WORDS + 1]; }
+    NT_DI int flags(int k) const { return tab[k * IKS_WORDS + 2]; }
+    NT_DI float weight(int k) const { return reinterpret_cast<const float*>(tab)[k * IKS_WORDS + 3]; }
+    NT_DI float offset(int k, int i) const { return reinterpret_cast<const float*>(tab)[k * IKS_WORDS + 4 + i]; }
+    NT_DI int link_joint(int k) const { return tab[k * IKS_WORDS + 8]; }
+    NT_DI int roff(int k) const { return tab[k * IKS_WORDS + 9]; }
+    NT_DI int toff(int k) const { return tab[k * IKS_WORDS + 10]; }
+    NT_DI xform pose(int bq, int b) const { return c.lxf(Fld<7>{bq}, 0, c.a.m.nb, b); }
+    NT_DI vec3 S_lin(int d) const { return vec3(f.S(c.e, 0, d), f.S(c.e, 1, d), f.S(c.e, 2, d)); }
+    NT_DI vec3 S_ang(int d) const { return vec3(f.S(c.e, 3, d), f.S(c.e, 4, d), f.S(c.e, 5, d)); }
+    NT_DI float& A(int i, int j) const { return row(F.A + i * (i + 1) / 2 + j); }
+};
+
+// eval_fk's X_j of joint j from the coordinates in rows jq
+template <int EPB>
+NT_DI xform iks_joint_transform(const IksCtx<EPB>& s, int j, int jq) {
+    const Ctx<EPB>& c = s.c;
+    const int type = c.T.joint_type[j], ds = c.T.joint_qd_start[j], qs = c.T.joint_q_start[j];
+    const int lin = c.T.joint_lin_count[j], ang = c.T.joint_ang_count[j];
+    auto Q = [&](int i) { return s.row(jq + qs + i); };
+    if (type == JT_PRISMATIC) return xform(c.dof_axis(ds) * Q(0), quat_identity());
+    if (type == JT_REVOLUTE) return xform(vec3(), quat_from_axis_angle(c.dof_axis(ds), Q(0)));
+    if (type == JT_BALL) return xform(vec3(), quat(Q(0), Q(1), Q(2), Q(3)));
+    if (type == JT_FREE || type == JT_DISTANCE) return xform(vec3(Q(0), Q(1), Q(2)), quat(Q(3), Q(4), Q(5), Q(6)));
+    if (type == JT_D6) {
+        vec3 pos(0.0f);
+        quat rot = quat_identity();
+        for (int k = 0; k < lin; ++k) pos += c.dof_axis(ds + k) * Q(k);
+        if (ang == 1) rot = quat_from_axis_angle(c.dof_axis(ds + lin), Q(lin));
+        if (ang >= 2) {
+            vec3 a0, a1, a2;
+            rot = d6_multi_angular(ang, c.dof_axis(ds + lin), c.dof_axis(ds + lin + 1), ang == 3 ? c.dof_axis(ds + lin + 2) : vec3(), Q(lin),
+                                   Q(lin + 1), ang == 3 ? Q(lin + 2) : 0.0f, a0, a1, a2);
+        }
+        return xform(pos, rot);
+    }
+    return xform(vec3(), quat_identity());
+}
+
+// body_q[child] of joint j (rows bq) from its parent's pose in the same rows and the coordinates in rows jq
+template <int EPB>
+NT_DI void iks_fk_item(const IksCtx<EPB>& s, int j, int jq, int bq) {
+    const Ctx<EPB>& c = s.c;
+    const nt_model& m = c.a.m;
+    const int parent = c.T.joint_parent[j], child = c.T.joint_child[j];
+    xform X_wpj = c.plxf(c.L.jp, 0, m.nj, j);
+    if (parent >= 0) X_wpj = s.pose(bq, parent) * X_wpj;
+    const xform X_wc = (X_wpj * iks_joint_transform(s, j, jq)) * xform_inverse(c.plxf(c.L.jp, 7, m.nj, j));
+    c.st_lxf(Fld<7>{bq}, m.nb, child, X_wc);
+}
+
+template <int EPB>
+NT_DI void iks_fk(const IksCtx<EPB>& s, int max_depth, int jq, int bq) {
+    for (int lvl = 0; lvl <= max_depth; ++lvl) {
+        if (s.c.valid)
+            for (int j = s.c.slot; j < s.c.a.m.nj; j += s.c.nslot)
+                if (s.f.depth[j] == lvl) iks_fk_item(s, j, jq, bq);
+        __syncthreads();
+    }
+}
+
+// the residual blocks (rows R) at the poses in rows bq / coordinates in rows jq: an objective per slot-lane, a limit row per slot-lane
+template <int EPB>
+NT_DI void iks_residuals(const IksCtx<EPB>& s, int jq, int bq, int R) {
+    const Ctx<EPB>& c = s.c;
+    const nt_model& m = c.a.m;
+    for (int k = 0; k < s.count; ++k) {
+        const int type = s.type(k), ro = R + s.roff(k), to = s.F.T + s.toff(k);
+        const float w = s.weight(k);
+        if (type == NT_IK_JOINT_LIMIT) {
+            for (int d = c.slot; d < m.nd; d += c.nslot) {
+                const int j = s.f.dof_joint[d], jt = c.T.joint_type[j];
+                const float lo = s.row(to + d), hi = s.row(to + m.nd + d);
+                float r = 0.0f;
+                if ((jt == JT_PRISMATIC || jt == JT_REVOLUTE || jt == JT_D6) && lo < hi && fabsf(lo) < NT_MAXVAL && fabsf(hi) < NT_MAXVAL) {
+                    const float q = s.row(jq + c.T.joint_q_start[j] + d - c.T.joint_qd_start[j]);
+                    r = w * (fmaxw(0.0f, q - hi) - fmaxw(0.0f, lo - q));
+                }
+                s.row(ro + d) = r;
+            }
+            continue;
+        }
+        if (c.slot != k % c.nslot) continue;
+        const xform X = s.pose(bq, s.link(k));
+        if (type == NT_IK_POSITION) {
+            const vec3 P = xform_point(X, vec3(s.offset(k, 0), s.offset(k, 1), s.offset(k, 2)));
+            const vec3 r = (P - vec3(s.row(to), s.row(to + 1), s.row(to + 2))) * w;
+            s.row(ro) = r.x; s.row(ro + 1) = r.y; s.row(ro + 2) = r.z;
+            s.row(ro + 3) = P.x; s.row(ro + 4) = P.y; s.row(ro + 5) = P.z;
+        } else {
+            const quat target(s.row(to), s.row(to + 1), s.row(to + 2), s.row(to + 3));
+            quat qe = (X.q * quat(s.offset(k, 0), s.offset(k, 1), s.offset(k, 2), s.offset(k, 3))) * quat_inverse(target);
+            if ((s.flags(k) & NT_IK_CANONICALIZE) && qe.w < 0.0f) qe = quat(-qe.x, -qe.y, -qe.z, -qe.w);
+            const float w2 = w * 2.0f;
+            s.row(ro) = w2 * qe.x; s.row(ro + 1) = w2 * qe.y; s.row(ro + 2) = w2 * qe.z;
+        }
+    }
+}
+
+// C = |r|^2 / 2 over the residual rows of block R, in row order (every lane of the environment: the same sum)
+template <int EPB>
+NT_DI float iks_cost(const IksCtx<EPB>& s, int R) {
+    float acc = 0.0f;
+    for (int k = 0; k < s.count; ++k) {
+        const int n = s.type(k) == NT_IK_JOINT_LIMIT ? s.c.a.m.nd : 3, ro = R + s.roff(k);
+        for (int i = 0; i < n; ++i) {
+            const float r = s.row(ro + i);
+            acc += r * r;
+        }
+    }
+    return 0.5f * acc;
+}
+
+// the Jacobian rows of objective k (position / rotation) in column d, without the weight
+template <int EPB>
+NT_DI vec3 iks_col(const IksCtx<EPB>& s, int k, int d) {
+    if (s.type(k) == NT_IK_ROTATION) return s.S_ang(d);
+    const int ro = s.F.R + s.roff(k);
+    return s.S_lin(d) + cross(s.S_ang(d), vec3(s.row(ro + 3), s.row(ro + 4), s.row(ro + 5)));
+}
+
+// one entry of the lower triangle of J^T J (item < nA) or of g = J^T r: the objectives in order
+template <int EPB>
+NT_DI void iks_normal_item(const IksCtx<EPB>& s, int item) {
+    const bool is_g = item >= s.F.nA;
+    int i = 0, j = 0;
+    if (is_g) {
+        i = j = item - s.F.nA;
+    } else {
+        while ((i + 1) * (i + 2) / 2 <= item) ++i;
+        j = item - i * (i + 1) / 2;
+    }
+    const int ji = s.f.dof_joint[i], jj = s.f.dof_joint[j];
+    float acc = 0.0f;
+    for (int k = 0; k < s.count; ++k) {
+        const int type = s.type(k), ro = s.F.R + s.roff(k);
+        const float w = s.weight(k);
+        if (type == NT_IK_JOINT_LIMIT) {
+            const float r = s.row(ro + i);
+            if (i == j && r != 0.0f) acc += is_g ? w * r : w * w;
+            continue;
+        }
+        const int lj = s.link_joint(k);
+        if (!s.f.on_path(ji, lj) || !s.f.on_path(jj, lj)) continue;
+        const vec3 ci = iks_col(s, k, i) * w;
+        acc += is_g ? dot(ci, vec3(s.row(ro), s.row(ro + 1), s.row(ro + 2))) : dot(ci, iks_col(s, k, j) * w);
+    }
+    if (is_g) s.row(s.F.g + i) = acc;
+    else s.row(s.F.A + item) = acc;
+}
+
+// joint_q (+) step * delta of joint j: rows jq -> rows jq2
+template <int EPB>
+NT_DI void iks_retract_item(const IksCtx<EPB>& s, int j, float step) {
+    const Ctx<EPB>& c = s.c;
+    const nt_model& m = c.a.m;
+    const int type = c.T.joint_type[j], qs = c.T.joint_q_start[j], ds = c.T.joint_qd_start[j];
+    const int qe = j + 1 < m.nj ? c.T.joint_q_start[j + 1] : m.nc;
+    auto Q = [&](int i) { return s.row(s.F.J.jq + qs + i); };
+    auto Q2 = [&](int i) -> float& { return s.row(s.F.jq2 + qs + i); };
+    auto D = [&](int i) { return step * s.row(s.F.X + ds + i); };
+    if (type == JT_PRISMATIC || type == JT_REVOLUTE || type == JT_D6) {
+        for (int i = 0; i < qe - qs; ++i) Q2(i) = Q(i) + D(i);
+    } else if (type == JT_BALL) {
+        const quat q = normalize(iks_exp(vec3(D(0), D(1), D(2))) * quat(Q(0), Q(1), Q(2), Q(3)));
+        Q2(0) = q.x; Q2(1) = q.y; Q2(2) = q.z; Q2(3) = q.w;
+    } else if (type == JT_FREE || type == JT_DISTANCE) {
+        // the child pose in the parent anchor frame Y = X_j X_c^-1: its COM translates, it rotates about the COM; X_j' = Y' X_c
+        const xform X_c = c.plxf(c.L.jp, 7, m.nj, j);
+        const vec3 com = c.com(c.T.joint_child[j]);
+        const xform Y = xform(vec3(Q(0), Q(1), Q(2)), quat(Q(3), Q(4), Q(5), Q(6))) * xform_inverse(X_c);
+        const quat qy = normalize(iks_exp(vec3(D(3), D(4), D(5))) * Y.q);
+        const vec3 cy = xform_point(Y, com) + vec3(D(0), D(1), D(2));
+        const xform Xn = xform(cy - quat_rotate(qy, com), qy) * X_c;
+        Q2(0) = Xn.p.x; Q2(1) = Xn.p.y; Q2(2) = Xn.p.z;
+        Q2(3) = Xn.q.x; Q2(4) = Xn.q.y; Q2(5) = Xn.q.z; Q2(6) = Xn.q.w;
+    } else {
+        for (int i = 0; i < qe - qs; ++i) Q2(i) = Q(i);
+    }
+}
+
+template <int EPB>
+__global__ void __launch_bounds__(256) ik_solve_kernel(KArgs a, nt_ik_problem P, const float* joint_q_in, float* joint_q_out, float* lambda,
+                                                       float* cost, int iterations, float step) {
+    extern __shared__ __align__(16) float lds[];
+    const nt_model& m = a.m;
+    constexpr int N = Ctx<EPB>::N;
+    const IksLayout F = iks_layout(m, P, Ctx<EPB>::UNI);
+    Ctx<EPB> c(a, lds, F.rows);
+    int* extra = reinterpret_cast<int*>(lds + (size_t)F.rows * N) + topo_ints(m);
+    int* tab = extra + jm_table_ints(m);
+    c.up = reinterpret_cast<float*>(extra + iks_table_ints(m));
+    __syncthreads();
+    jm_build_tables(c, extra);
+    const JmCtx<EPB> f(c, F.J, extra);
+    const IksCtx<EPB> s(f, F, tab, P.count);
+    const int max_depth = f.max_depth(), nd = m.nd;
+    // the objective table (one thread; the loop index is uniform: the kernel arguments are read with scalar loads)
+    {
+        int roff = 0, toff = 0;
+        for (int k = 0; k < P.count; ++k) {
+            const nt_ik_objective& o = P.obj[k];
+            if (threadIdx.x == 0) {
+                int lj = 0;
+                for (int j = 0; j < m.nj; ++j)
+                    if (c.T.joint_child[j] == o.link) lj = j;
+                int* t = tab + k * IKS_WORDS;
+                float* tf = reinterpret_cast<float*>(t);
+                t[0] = o.type; t[1] = o.link; t[2] = o.flags; tf[3] = o.weight;
+                tf[4] = o.offset[0]; tf[5] = o.offset[1]; tf[6] = o.offset[2]; tf[7] = o.offset[3];
+                t[8] = lj; t[9] = roff; t[10] = toff; t[11] = 0;
+            }
+            const int nt = iks_tgt_rows(o.type, nd);
+            if (c.valid)
+                for (int r = c.slot; r < nt; r += c.nslot) s.row(F.T + toff + r) = o.target[(size_t)c.env * nt + r];
+            roff += iks_res_rows(o.type, nd);
+            toff += nt;
+        }
+    }
+    load_params(c, false);
+    if (c.valid)
+        for (int i = c.slot; i < m.nc; i += c.nslot) s.row(F.J.jq + i) = joint_q_in[(size_t)c.env * m.nc + i];
+    float lam = c.valid ? lambda[c.env] : 1.0f;
+    __syncthreads();
+    iks_fk(s, max_depth, F.J.jq, c.L.bq.off);
+    if (c.valid) iks_residuals(s, F.J.jq, c.L.bq.off, F.R);
+    __syncthreads();
+    float C = c.valid ? iks_cost(s, F.R) : 0.0f;
+    for (int it = 0; it < iterations; ++it) {
+        if (c.valid)
+            for (int d = c.slot; d < nd; d += c.nslot) jm_S_item(f, d, vec3());
+        __syncthreads();
+        if (c.valid)
+            for (int item = c.slot; item < F.nA + nd; item += c.nslot) iks_normal_item(s, item);
+        __syncthreads();
+        // Cholesky of A + lambda I in place, column by column: the pivot by every lane, the column's rows dealt to the slot-lanes
+        bool bad = false;
+        for (int j = 0; j < nd; ++j) {
+            if (c.valid) {
+                float p = s.A(j, j) + lam;
+                for (int k = 0; k < j; ++k) {
+                    const float l = s.A(j, k);
+                    p -= l * l;
+                }
+                if (!(p > 0.0f)) {
+                    bad = true;
+                    p = 1.0f;
+                }
+                p = sqrtf(p);
+                if (c.slot == 0) s.row(F.Dg + j) = p;
+                for (int i = j + 1 + c.slot; i < nd; i += c.nslot) {
+                    float t = s.A(i, j);
+                    for (int k = 0; k < j; ++k) t -= s.A(i, k) * s.A(j, k);
+                    s.A(i, j) = t / p;
+                }
+            }
+            __syncthreads();
+        }
+        // L y = -g, L^T delta = y (one lane: each sum in ascending order)
+        if (c.valid && c.slot == 0) {
+            for (int i = 0; i < nd; ++i) {
+                float t = -s.row(F.g + i);
+                for (int k = 0; k < i; ++k) t -= s.A(i, k) * s.row(F.X + k);
+                s.row(F.X + i) = t / s.row(F.Dg + i);
+            }
+            for (int i = nd - 1; i >= 0; --i) {
+                float t = s.row(F.X + i);
+                for (int k = i + 1; k < nd; ++k) t -= s.A(k, i) * s.row(F.X + k);
+                s.row(F.X + i) = t / s.row(F.Dg + i);
+            }
+        }
+        __syncthreads();
+        if (c.valid)
+            for (int j = c.slot; j < m.nj; j += c.nslot) iks_retract_item(s, j, step);
+        __syncthreads();
+        iks_fk(s, max_depth, F.jq2, F.bq2);
+        if (c.valid) iks_residuals(s, F.jq2, F.bq2, F.R2);
+        __syncthreads();
+        bool accept = false;
+        float C2 = 0.0f;
+        if (c.valid) {
+            C2 = iks_cost(s, F.R2);
+            float dd = 0.0f, gd = 0.0f;
+            for (int i = 0; i < nd; ++i) {
+                const float x = s.row(F.X + i);
+                dd += x * x;
+                gd += s.row(F.g + i) * x;
+            }
+            const float pred = 0.5f * step * (step * lam * dd - (2.0f - step) * gd);
+            accept = !bad && pred > 0.0f && C2 < C && (C - C2) / pred > P.rho_min;
+        }
+        __syncthreads();  // (every lane has read delta, g and the candidate's residuals)
+        if (accept) {
+            for (int i = c.slot; i < m.nc; i += c.nslot) s.row(F.J.jq + i) = s.row(F.jq2 + i);
+            for (int i = c.slot; i < 7 * m.nb; i += c.nslot) s.row(c.L.bq.off + i) = s.row(F.bq2 + i);
+            for (int i = c.slot; i < F.nR; i += c.nslot) s.row(F.R + i) = s.row(F.R2 + i);
+            C = C2;
+            lam = fmaxw(lam / P.lambda_factor, P.lambda_min);
+        } else {
+            lam = fminw(lam * P.lambda_factor, P.lambda_max);
+        }
+        __syncthreads();
+    }
+    if (!c.valid) return;
+    for (int i = c.slot; i < m.nc; i += c.nslot) joint_q_out[(size_t)c.env * m.nc + i] = s.row(F.J.jq + i);
+    if (c.slot == 0) {
+        lambda[c.env] = lam;
+        cost[c.env] = C;
+    }
+}
+
 }  // namespace ieee
 }  // namespace
 
@@ -741,6 +1113,57 @@ nt_status nt_eval_mass_matrix_tile(const nt_model* m, const nt_state* in, float*
 
 nt_status nt_eval_mass_matrix(const nt_model* m, const nt_state* in, float* H, float* body_I_s, const uint8_t* art_mask, void* stream) {
     return nt_eval_mass_matrix_tile(m, in, H, body_I_s, art_mask, 0, stream);
+}
+
+// nt_ik_solve: tile rule as nt_eval_ik_tile's
+nt_status nt_ik_solve_tile(const nt_model* m, const nt_ik_problem* p, const float* joint_q_in, float* joint_q_out, float* lambda, float* cost,
+                           int32_t iterations, float step_size, int32_t envs_per_block, void* stream) {
+    if (!model_ok(m) || !p || !joint_q_in || !joint_q_out || !lambda || !cost || iterations < 0 || p->count < 0) return NT_ERR_INVALID_ARG;
+    if (m->nj <= 0 || m->na <= 0 || m->nd <= 0 || !m->art_start || p->count > NT_IK_MAX_OBJECTIVES) return NT_ERR_UNSUPPORTED;
+    for (int k = 0; k < p->count; ++k) {
+        const nt_ik_objective& o = p->obj[k];
+        if (!o.target) return NT_ERR_INVALID_ARG;
+        if (o.type != NT_IK_POSITION && o.type != NT_IK_ROTATION && o.type != NT_IK_JOINT_LIMIT) return NT_ERR_UNSUPPORTED;
+        if (o.type != NT_IK_JOINT_LIMIT && (o.link < 0 || o.link >= m->nb)) return NT_ERR_UNSUPPORTED;
+    }
+#ifdef NT_DEV_FAST
+    return NT_ERR_UNSUPPORTED;
+#else
+    KArgs a = {};
+    a.m = *m;
+    const size_t shared_ints = (size_t)topo_ints(*m) + iks_table_ints(*m);
+    auto bytes = [&](int epb, bool uni) {
+        return tile_bytes(iks_layout(*m, *p, uni).rows, epb, shared_ints, uni ? make_layout(*m, false, false, true, false).uni_floats : 0);
+    };
+    const bool uni = envs_per_block == 0 && m->params_uniform && bytes(16, true) <= LDS_BYTES_PER_CU;
+    int epb = 0;
+    if (uni) {
+        epb = 16;
+    } else if (envs_per_block == 0) {
+        const int cands[4] = {16, 8, 4, 1};
+        for (int i = 0; i < 4 && !epb; ++i)
+            if (bytes(cands[i], false) <= LDS_BYTES_PER_CU) epb = cands[i];
+    } else if ((envs_per_block == 1 || envs_per_block == 4 || envs_per_block == 8 || envs_per_block == 16) &&
+               bytes(envs_per_block, false) <= LDS_BYTES_PER_CU) {
+        epb = envs_per_block;
+    }
+    if (!epb) return NT_ERR_UNSUPPORTED;
+    // slot-lanes: one per entry of the normal equations (the widest phase)
+    const int want = imax(imax(m->nb, m->nj), m->nd * (m->nd + 1) / 2 + m->nd), cap = 256 / epb;
+    a.nslot = want < cap ? want : cap;
+    if (uni)
+        return launch_tile(ik_solve_kernel<16 + NT_UNI>, a, 16, bytes(16, true), (hipStream_t)stream, *p, joint_q_in, joint_q_out, lambda, cost,
+                           (int)iterations, step_size);
+    return dispatch_epb(Epbs<16, 8, 4, 1>{}, epb, [&](auto E) {
+        return launch_tile(ik_solve_kernel<E>, a, E, bytes(E, false), (hipStream_t)stream, *p, joint_q_in, joint_q_out, lambda, cost,
+                           (int)iterations, step_size);
+    });
+#endif
+}
+
+nt_status nt_ik_solve(const nt_model* m, const nt_ik_problem* p, const float* joint_q_in, float* joint_q_out, float* lambda, float* cost,
+                      int32_t iterations, float step_size, void* stream) {
+    return nt_ik_solve_tile(m, p, joint_q_in, joint_q_out, lambda, cost, iterations, step_size, 0, stream);
 }
 
 #ifdef NT_PHASE_TIMING
