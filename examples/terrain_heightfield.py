@@ -77,10 +77,20 @@ def main():
             state_0, state_1 = state_1, state_0
     q = state_0.body_q.cpu().numpy().reshape(-1, 7)
     wall = time.perf_counter() - t0
+    # a height scan under body 0 of every world: 5 x 5 rays pointing down from 0.3 m above the body, which ignore the body's own shape
+    # (one launch; `scan.distance` stays on the device for a policy to read)
+    grid = np.linspace(-0.2, 0.2, 5)
+    origins = np.array([[x, y, 0.3] for x in grid for y in grid], np.float32)
+    scan = nt.sensors.SensorRaycast(model, origins, np.tile(np.float32([0.0, 0.0, -1.0]), (len(origins), 1)), ray_body=0, max_distance=5.0,
+                                    exclude_bodies=(0,))
+    scan.eval(state_0)
+    heights_below = scan.distance.cpu().numpy()
     clearance = q[:, 2] - surface(q[:, 0], q[:, 1])
     print(f"{args.worlds} worlds x {len(spots)} shapes on a {'mesh' if args.mesh else 'heightfield'} terrain: {args.frames} frames in {wall:.2f} s "
           f"({args.worlds * args.frames * args.substeps / wall / 1e6:.3f} M env-steps/s incl. Python); clearance above the surface "
           f"min {clearance.min():.3f} m, max {clearance.max():.3f} m; contacts in the last substep {int(contacts.rigid_contact_count.item())}")
+    print(f"height scan under body 0: {heights_below.shape[1]} rays per world, {np.mean(heights_below >= 0.0):.2f} of them hit, "
+          f"mean distance {heights_below[heights_below >= 0.0].mean():.3f} m")
     assert np.all(np.isfinite(q)) and clearance.min() > 0.02, "a shape fell through the terrain"
 
 

@@ -121,6 +121,90 @@ typedef struct {
 #define NT_PAIR_KIND_MESH_TRIANGLE 3
 nt_status nt_mesh_triangle_pairs(const nt_mesh_triangle_args* args, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * nt_raycast: R rays per world against the shapes of that world, one launch (newton_amd.sensors.SensorRaycast; the capability of
+ * the reference's newton.sensors.SensorRaycast, which is ONE camera -- here one sensor per world of the batched layout).
+ *
+ * Rays.  Ray r is an origin o_r, a direction d_r and a frame ray_body[r]: an env-local body index, or -1 for the world frame.  With
+ * (p, q) = body_q[ray_body[r]] of the world: O = p + rot(q, o_r), D = normalize(rot(q, d_r)) (world frame: O = o_r, D = normalize(d_r)).
+ * A direction of length 0 is a miss, and so is a ray_body outside -1 .. nb - 1.  Only nt_state.body_q is read.  origins / directions
+ * are one [R][3] pattern shared by every world (rays_per_world = 0) or [env_count][R][3] (rays_per_world = 1); they are read through
+ * the pointers at launch time, so an in-place update followed by a graph replay takes effect (the convention of nt_ik_solve's targets).
+ *
+ * Targets.  An env-uniform selection of the ns + ng shape slots (env-local shapes, then global shapes).  The byte mask of the Python
+ * interface arrives as the ascending list of the selected slots with their GeoType: `targets` [target_count][2] = (slot, type) in
+ * device memory, and `targets_host`, the same table in host memory -- the entry point does not synchronise, so what it checks before
+ * the launch (slots ascending and inside 0 .. ns + ng - 1, supported types, the LDS fit) it checks on the host copy.  The type is
+ * Model.shape_type: MESH and HFIELD are named as such (nt_model.shape_type folds both into CONVEX_MESH for the tiles).  The pose of a
+ * shape is body_q[shape_body] * shape xform (shape_param rows 0..6; global shapes: gshape_param), its scale comes from the same tables.
+ *
+ * Only surfaces that FACE the ray count: with the outward unit normal n at the hit, a hit needs n . D < 0 and 0 <= t <= max_distance.
+ * An origin inside a closed shape does not hit that shape; mesh triangles are back-face culled by winding; a heightfield is hit on
+ * its top surface only; a plane from its front side only.  In the shape frame (o, d):
+ *   PLANE      z = 0, n = +z.  Infinite when scale x = y = 0 (the routing rule above), else |x| <= scale x, |y| <= scale y.
+ *   SPHERE, ELLIPSOID   radii scale xyz (sphere: scale x three times).  Cast in the space scaled to the unit sphere: o / radii, d / radii
+ *              (t is unchanged), the ray moved to its point nearest the centre first, disc = 1 - |c|^2 > 0 (a tangent ray misses);
+ *              n = normalize(p_unit / radii), the inverse-transpose scale.
+ *   BOX        half extents scale xyz: slab test from the ray's point nearest the centre, n = the entered face (first axis on a tie);
+ *              needs t_enter < t_exit.
+ *   CAPSULE    radius scale x, half height scale y along z (nt_primitives.hpp / nt_convex.hpp): the entering root on the infinite
+ *              cylinder (2-D, from the point nearest the axis); |z| <= half height there: the lateral surface, else the hemisphere
+ *              of that end.  A ray parallel to the axis takes the hemisphere it runs towards.
+ *   CYLINDER   the same lateral surface; beyond the ends the cap disc z = +-half height, x^2 + y^2 <= r^2.  Straight cylinders only
+ *              (scale z, the barrel radius, = 0): the scale is per-world device data the entry point cannot see, the caller vouches
+ *              (SensorRaycast checks the host model and refuses a barrel).
+ *   CONE       apex at z = +half height, base radius scale x at z = -half height: x^2 + y^2 = (k w)^2, k = r / (2 h), w = h - z in
+ *              (0, 2 h], n = (x, y, k^2 w), roots by the cancellation-free form q = -(B + sign(B) sqrt(B^2 - A C)), t = q / A, C / q;
+ *              and the base disc.  The nearest facing candidate.
+ *   MESH       every triangle of shape_triangle_range, vertices times shape scale, Moeller-Trumbore in fp32 in the mesh frame,
+ *              det = e1 . (d x e2) > 0 (front face by winding), 0 <= u, 0 <= v, u + v <= det.  With block_bounds, blocks of
+ *              NT_MESH_TRIANGLE_BLOCK triangles whose (padded) box the ray misses are skipped: the same hit set.
+ *   HFIELD     the two triangles per cell of the triangle leg (tri_sub 0 = (p00, p10, p11), 1 = (p00, p11, p01); index
+ *              (row (ncol - 1) + col) 2 + tri_sub), the same test.  The ray is clipped to the field's box and the cells are visited
+ *              by a 2-D walk along the ray: one slab of the faster grid axis after the other, the one to three cells the ray can touch
+ *              in it; the walk ends once a hit lies before the end of the slab.  The shape scale is not applied (as in the triangle leg).
+ * CONVEX_MESH (the model stores vertices only), GAUSSIAN and barrel cylinders are no ray targets: NT_ERR_UNSUPPORTED.
+ *
+ * Result per (world, ray): the nearest hit; a tie in t goes to the lower Newton shape id, within one mesh / heightfield to the lower
+ * triangle index.  distance [env_count][R]: t, or -1 for a miss; normal [env_count][R][3] (or NULL): unit, world frame, zeros on a
+ * miss; shape [env_count][R] (or NULL): the Newton shape id, or -1.  world_mask ([env_count] bytes or NULL): rows of unselected worlds
+ * are neither computed nor written.  Every value is produced by ONE lane, which visits the targets in ascending slot order
+ * (primitives, then meshes and heightfields) and the triangles of a mesh in ascending index; IEEE arithmetic, no atomics: identical
+ * worlds give identical bits, and the result does not depend on the launch geometry.
+ *
+ * Same conventions as newton_hip.h: device pointers owned by the caller, no allocation, no synchronisation, recordable by
+ * nt_graph_capture_begin / _end.  Errors: null model / state / args / body_q / rays / distance / target tables, ray_count <= 0,
+ * target_count < 0, a MESH or HFIELD target without its tables: NT_ERR_INVALID_ARG; a target list that is not ascending or leaves the
+ * slots: NT_ERR_INVALID_ARG; an unsupported target type, or staged targets (48 bytes each per world) beyond the CU's LDS:
+ * NT_ERR_UNSUPPORTED.
+ * --------------------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t ray_count;                 /* R, rays per world */
+    int32_t rays_per_world;            /* 0: origins / directions are [R][3], shared; 1: [env_count][R][3] */
+    const float* origins;
+    const float* directions;
+    const int32_t* ray_body;           /* [R] env-local body index or -1 (world frame) */
+    float max_distance;
+    int32_t target_count;              /* K selected shape slots */
+    const int32_t* targets;            /* DEVICE [K][2] (slot, GeoType), ascending slot */
+    const int32_t* targets_host;       /* HOST   [K][2] the same table (checked before the launch) */
+    const uint8_t* world_mask;         /* [env_count] or NULL */
+    float* distance;                   /* [env_count][R] */
+    float* normal;                     /* [env_count][R][3] or NULL */
+    int32_t* shape;                    /* [env_count][R] or NULL */
+    /* mesh / heightfield tables, indexed by Newton shape id, field meanings of nt_mesh_triangle_args; NULL when no target needs them */
+    const int32_t* shape_vertex_range;
+    const int32_t* shape_triangle_range;
+    const float* vertices;
+    const int32_t* indices;
+    const float* block_bounds;         /* or NULL: no block skipping */
+    const int32_t* shape_block_start;  /* (both or neither) */
+    const int32_t* shape_heightfield_index;
+    const nt_heightfield* heightfields;
+    const float* elevations;
+} nt_raycast_args;
+nt_status nt_raycast(const nt_model* m, const nt_state* s, const nt_raycast_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

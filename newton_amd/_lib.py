@@ -170,6 +170,16 @@ class nt_mesh_triangle_args(C.Structure):
                 ("elevations", C.c_void_p)]
 
 
+class nt_raycast_args(C.Structure):
+    """include/newton_hip_mesh.h: rays per world against the selected shapes (newton_amd.sensors.SensorRaycast)."""
+    _fields_ = [("ray_count", C.c_int32), ("rays_per_world", C.c_int32), ("origins", C.c_void_p), ("directions", C.c_void_p),
+                ("ray_body", C.c_void_p), ("max_distance", C.c_float), ("target_count", C.c_int32), ("targets", C.c_void_p),
+                ("targets_host", C.c_void_p), ("world_mask", C.c_void_p), ("distance", C.c_void_p), ("normal", C.c_void_p),
+                ("shape", C.c_void_p), ("shape_vertex_range", C.c_void_p), ("shape_triangle_range", C.c_void_p), ("vertices", C.c_void_p),
+                ("indices", C.c_void_p), ("block_bounds", C.c_void_p), ("shape_block_start", C.c_void_p),
+                ("shape_heightfield_index", C.c_void_p), ("heightfields", C.c_void_p), ("elevations", C.c_void_p)]
+
+
 class nt_sdf(C.Structure):
     _fields_ = [("coarse", C.c_void_p), ("subgrid", C.c_void_p), ("slots", C.c_void_p), ("cx", C.c_int32), ("cy", C.c_int32),
                 ("cz", C.c_int32), ("tex_size", C.c_int32), ("subgrid_size", C.c_int32), ("quantization", C.c_int32),
@@ -403,6 +413,7 @@ SYMBOLS = {
     # include/newton_hip_mesh.h
     "nt_mesh_plane_pairs": (C.c_int32, [C.POINTER(nt_mesh_plane_args), _P]),
     "nt_mesh_triangle_pairs": (C.c_int32, [C.POINTER(nt_mesh_triangle_args), _P]),
+    "nt_raycast": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_state), C.POINTER(nt_raycast_args), _P]),
     # include/newton_hip_broadphase.h
     "nt_broadphase_nxn_swept": (C.c_int32, [C.POINTER(nt_broadphase_in), C.POINTER(nt_broadphase_motion), _P, _P, C.c_int32, C.c_int32,
                                             C.c_int32, _P, _P, C.c_int32, _P]),

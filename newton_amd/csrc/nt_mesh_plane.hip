@@ -1,4 +1,5 @@
 // nt_mesh_plane.hip -- MESH vs infinite plane for gfx950: the vertex leg of CollisionPipeline.collide (include/newton_hip_mesh.h).
+// Also home of raycast_kernel / nt_raycast (further down): a unit of the mesh legs with the default scheduler, nt_math.hpp and the mesh tables' header.
 //
 // Reference behaviour (paths under /root/reference/newton/_src/geometry):
 //   routing      narrow_phase.py:618-631     (infinite plane, mesh) pairs -> shape_pairs_mesh_plane, stored (mesh, plane)
@@ -211,6 +212,425 @@ __global__ void __launch_bounds__(256) mesh_plane_pairs_kernel(nt_mesh_plane_arg
     }
 }
 
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// nt_raycast (newton_amd.sensors.SensorRaycast; contract: include/newton_hip_mesh.h): R rays per world against the selected shapes.
+//
+// MI355X mapping.  A workgroup of 256 lanes serves `wpb` worlds (4 / 2 / 1 for R <= 64 / 128 / more) with `rl` = 256 / wpb lanes each.
+// It stages the selected targets of its worlds once in LDS -- world pose (body_q * shape xform), scale, type, Newton id: RC_REC = 12
+// words per (world, target), read from the env-major tables with one (world, target) per lane -- and after one barrier every lane
+// owns one ray (rays r, r + rl, ... when R > rl): it loads its ray, puts it into the world frame from body_q, and walks the staged
+// records in ascending slot order.  All lanes of a world read the SAME record at the same time: an LDS broadcast, no bank conflicts.
+// Meshes and heightfields follow in a second pass over the records; their vertices, indices, block bounds and elevations come from
+// HBM / L2 (shared by every world of a replicated scene).  One lane produces every value of a ray: no atomics, no cross-lane
+// reduction, so the launch geometry cannot change a bit.  What bounds it: LDS only for thousands of targets (48 B each per world);
+// the primitive pass is ALU work on broadcast records, the mesh pass is divergent L2 latency (every lane walks its own blocks).
+// ------------------------------------------------------------------------------------------------------------------------------
+constexpr int RC_REC = 12;  // staged words per (world, target): p[3] q[4] scale[3] type id
+constexpr int RC_THREADS = 256;
+constexpr size_t RC_LDS_BYTES_PER_CU = 160 * 1024;
+constexpr int RC_PLANE = 1, RC_HFIELD = 2, RC_SPHERE = 3, RC_CAPSULE = 4, RC_ELLIPSOID = 5, RC_CYLINDER = 6, RC_BOX = 7, RC_MESH = 8, RC_CONE = 9;
+constexpr float RC_INF = 3.0e38f;
+
+struct RcBest {  // the nearest hit so far: t, Newton shape id, staged record, unnormalised normal in the shape frame
+    float t;
+    int id, k;
+    vec3 n;
+};
+
+NT_DI void rc_offer(RcBest& b, float max_distance, float t, int id, int k, vec3 n) {
+    if (!(t >= 0.0f) || !(t <= max_distance)) return;
+    if (t < b.t || (t == b.t && id < b.id)) { b.t = t; b.id = id; b.k = k; b.n = n; }
+}
+
+// entering root of |o + t d| = radius, from the ray's point nearest the centre; p = hit point relative to the centre
+NT_DI bool rc_sphere(vec3 o, vec3 d, float radius, float& t, vec3& p) {
+    const float a = dot(d, d);
+    const float t0 = -dot(o, d) / a;
+    const vec3 c = o + d * t0;
+    const float disc = radius * radius - dot(c, c);
+    if (!(disc > 0.0f)) return false;
+    const float h = sqrtf(disc / a);
+    t = t0 - h;
+    p = c - d * h;
+    return true;
+}
+
+// entering root on the infinite cylinder x^2 + y^2 = r^2 (2-D, from the point nearest the axis).  0: miss, 1: root, 2: parallel inside
+NT_DI int rc_lateral(vec3 o, vec3 d, float r, float& t) {
+    const float a = d.x * d.x + d.y * d.y;
+    if (!(a > 0.0f)) return (o.x * o.x + o.y * o.y < r * r) ? 2 : 0;
+    const float t0 = -(o.x * d.x + o.y * d.y) / a;
+    const float cx = o.x + d.x * t0, cy = o.y + d.y * t0;
+    const float disc = r * r - (cx * cx + cy * cy);
+    if (!(disc > 0.0f)) return 0;
+    t = t0 - sqrtf(disc / a);
+    return 1;
+}
+
+NT_DI bool rc_capsule(vec3 o, vec3 d, float r, float hh, float& t, vec3& n) {
+    float tl = 0.0f;
+    const int lat = rc_lateral(o, d, r, tl);
+    if (lat == 0) return false;
+    float end;  // which hemisphere
+    if (lat == 1) {
+        const float z = o.z + d.z * tl;
+        if (fabsf(z) <= hh) { t = tl; n = vec3(o.x + d.x * tl, o.y + d.y * tl, 0.0f); return true; }
+        end = z > 0.0f ? hh : -hh;
+    } else {
+        end = d.z < 0.0f ? hh : -hh;
+    }
+    vec3 p;
+    if (!rc_sphere(vec3(o.x, o.y, o.z - end), d, r, t, p)) return false;
+    if (p.z * end < 0.0f) return false;  // (the inner half of the end sphere: not the capsule's surface)
+    n = p;
+    return true;
+}
+
+NT_DI bool rc_cylinder(vec3 o, vec3 d, float r, float hh, float& t, vec3& n) {
+    float tl = 0.0f;
+    const int lat = rc_lateral(o, d, r, tl);
+    if (lat == 0) return false;
+    float end;
+    if (lat == 1) {
+        const float z = o.z + d.z * tl;
+        if (fabsf(z) <= hh) { t = tl; n = vec3(o.x + d.x * tl, o.y + d.y * tl, 0.0f); return true; }
+        end = z > 0.0f ? hh : -hh;
+    } else {
+        end = d.z < 0.0f ? hh : -hh;
+    }
+    if (!(d.z * end < 0.0f)) return false;  // the cap has to face the ray
+    t = (end - o.z) / d.z;
+    const float x = o.x + d.x * t, y = o.y + d.y * t;
+    if (!(x * x + y * y <= r * r)) return false;
+    n = vec3(0.0f, 0.0f, end);
+    return true;
+}
+
+NT_DI bool rc_box(vec3 o, vec3 d, vec3 half, float& t, vec3& n) {
+    const float t0 = -dot(o, d) / dot(d, d);
+    const vec3 c = o + d * t0;
+    float t_in = -RC_INF, t_out = RC_INF;
+    int axis = 0;
+#define RC_SLAB(I, C, D, H)                                   \
+    if ((D) != 0.0f) {                                        \
+        const float ta = (-(H) - (C)) / (D), tb = ((H) - (C)) / (D); \
+        const float tn = fminw(ta, tb), tf = fmaxw(ta, tb);   \
+        if (tn > t_in) { t_in = tn; axis = (I); }             \
+        t_out = fminw(t_out, tf);                             \
+    } else if (fabsf(C) > (H)) {                              \
+        return false;                                         \
+    }
+    RC_SLAB(0, c.x, d.x, half.x)
+    RC_SLAB(1, c.y, d.y, half.y)
+    RC_SLAB(2, c.z, d.z, half.z)
+#undef RC_SLAB
+    if (!(t_in < t_out)) return false;
+    t = t0 + t_in;
+    const float da = vget(d, axis);
+    n = vec3();
+    vset(n, axis, da > 0.0f ? -1.0f : 1.0f);
+    return true;
+}
+
+NT_DI bool rc_cone(vec3 o, vec3 d, float r, float hh, float& t, vec3& n) {
+    const float t0 = -dot(o, d) / dot(d, d);
+    const vec3 c = o + d * t0;
+    const float k = hh > 0.0f ? r / (2.0f * hh) : 0.0f, k2 = k * k;
+    const float w0 = hh - c.z;
+    const float A = d.x * d.x + d.y * d.y - k2 * d.z * d.z;
+    const float B = c.x * d.x + c.y * d.y + k2 * w0 * d.z;
+    const float C = c.x * c.x + c.y * c.y - k2 * w0 * w0;
+    float best = RC_INF;
+    vec3 bn;
+    const float disc = B * B - A * C;
+    if (disc >= 0.0f) {
+        const float q = -(B + (B < 0.0f ? -1.0f : 1.0f) * sqrtf(disc));
+        for (int i = 0; i < 2; ++i) {
+            if ((i == 0 ? A : q) == 0.0f) continue;
+            const float tr = i == 0 ? q / A : C / q;
+            const float w = w0 - tr * d.z;
+            if (!(w > 0.0f) || !(w <= 2.0f * hh)) continue;
+            const vec3 nn(c.x + d.x * tr, c.y + d.y * tr, k2 * w);
+            if (!(dot(nn, d) < 0.0f)) continue;
+            if (tr < best) { best = tr; bn = nn; }
+        }
+    }
+    if (d.z > 0.0f) {  // the base disc, facing -z
+        const float tr = (-hh - c.z) / d.z;
+        const float x = c.x + d.x * tr, y = c.y + d.y * tr;
+        if (x * x + y * y <= r * r && tr < best) { best = tr; bn = vec3(0.0f, 0.0f, -1.0f); }
+    }
+    if (!(best < RC_INF)) return false;
+    t = t0 + best;
+    n = bn;
+    return true;
+}
+
+// one primitive in its own frame
+NT_DI bool rc_primitive(int type, vec3 s, vec3 o, vec3 d, float& t, vec3& n) {
+    if (type == RC_PLANE) {
+        if (!(d.z < 0.0f)) return false;
+        t = -o.z / d.z;
+        if (s.x != 0.0f || s.y != 0.0f) {
+            const float x = o.x + d.x * t, y = o.y + d.y * t;
+            if (!(fabsf(x) <= s.x) || !(fabsf(y) <= s.y)) return false;
+        }
+        n = vec3(0.0f, 0.0f, 1.0f);
+        return true;
+    }
+    if (type == RC_SPHERE || type == RC_ELLIPSOID) {
+        const vec3 rad = type == RC_SPHERE ? vec3(s.x, s.x, s.x) : s;
+        vec3 p;
+        if (!rc_sphere(vec3(o.x / rad.x, o.y / rad.y, o.z / rad.z), vec3(d.x / rad.x, d.y / rad.y, d.z / rad.z), 1.0f, t, p)) return false;
+        n = vec3(p.x / rad.x, p.y / rad.y, p.z / rad.z);
+        return true;
+    }
+    if (type == RC_BOX) return rc_box(o, d, s, t, n);
+    if (type == RC_CAPSULE) return rc_capsule(o, d, s.x, s.y, t, n);
+    if (type == RC_CYLINDER) return rc_cylinder(o, d, s.x, s.y, t, n);
+    if (type == RC_CONE) return rc_cone(o, d, s.x, s.y, t, n);
+    return false;
+}
+
+// Moeller-Trumbore, front faces only (det > 0 <=> n . d < 0 for n = e1 x e2), edges inclusive
+NT_DI bool rc_triangle(vec3 o, vec3 d, vec3 v0, vec3 v1, vec3 v2, float& t, vec3& n) {
+    const vec3 e1 = v1 - v0, e2 = v2 - v0;
+    const vec3 pvec = cross(d, e2);
+    const float det = dot(e1, pvec);
+    if (!(det > 0.0f)) return false;
+    const vec3 tvec = o - v0;
+    const float u = dot(tvec, pvec);
+    if (u < 0.0f || u > det) return false;
+    const vec3 qvec = cross(tvec, e1);
+    const float v = dot(d, qvec);
+    if (v < 0.0f || u + v > det) return false;
+    t = dot(e2, qvec) / det;
+    n = cross(e1, e2);
+    return true;
+}
+
+// the t range of the ray inside the box [lo, hi]; false: it misses the box
+NT_DI bool rc_clip(vec3 o, vec3 d, vec3 lo, vec3 hi, float& t_in, float& t_out) {
+#define RC_CLIP(O, D, LO, HI)                                              \
+    if ((D) != 0.0f) {                                                     \
+        const float ta = ((LO) - (O)) / (D), tb = ((HI) - (O)) / (D);       \
+        t_in = fmaxw(t_in, fminw(ta, tb));                                 \
+        t_out = fminw(t_out, fmaxw(ta, tb));                               \
+    } else if ((O) < (LO) || (O) > (HI)) {                                 \
+        return false;                                                      \
+    }
+    RC_CLIP(o.x, d.x, lo.x, hi.x)
+    RC_CLIP(o.y, d.y, lo.y, hi.y)
+    RC_CLIP(o.z, d.z, lo.z, hi.z)
+#undef RC_CLIP
+    return t_in <= t_out;
+}
+
+NT_DI vec3 rc_ld3(const float* p) { return vec3(p[0], p[1], p[2]); }
+
+// every triangle of mesh shape `id` in ascending index (ties keep the lower index); blocks whose padded box the ray misses are skipped
+NT_DI void rc_mesh(const nt_raycast_args& a, int id, int k, vec3 s, vec3 o, vec3 d, float max_distance, RcBest& best) {
+    const int v0 = a.shape_vertex_range[2 * (size_t)id], nv = a.shape_vertex_range[2 * (size_t)id + 1];
+    const int t0 = a.shape_triangle_range[2 * (size_t)id], ntri = a.shape_triangle_range[2 * (size_t)id + 1];
+    const bool blocks = a.block_bounds != nullptr && a.shape_block_start != nullptr;
+    float bt = RC_INF;
+    vec3 bn;
+    for (int b0 = 0; b0 < ntri; b0 += NT_MESH_TRIANGLE_BLOCK) {
+        if (blocks) {
+            const float* bb = a.block_bounds + 6 * (size_t)(a.shape_block_start[id] + b0 / NT_MESH_TRIANGLE_BLOCK);
+            const vec3 c0 = cw_mul(rc_ld3(bb), s), c1 = cw_mul(rc_ld3(bb + 3), s);
+            vec3 lo = vmin(c0, c1), hi = vmax(c0, c1);
+            // padded far beyond the rounding of the triangle test (1e-7 relative): the skip never removes a hit
+            const vec3 ao = vabs(o);
+            const float pad = 1.0e-4f * (fmaxw(fmaxw(ao.x, ao.y), ao.z) + length(hi - lo)) + 1.0e-6f;
+            lo = lo - vec3(pad);
+            hi = hi + vec3(pad);
+            float t_in = -pad, t_out = max_distance + pad;
+            if (!rc_clip(o, d, lo, hi, t_in, t_out)) continue;
+        }
+        const int b1 = b0 + NT_MESH_TRIANGLE_BLOCK < ntri ? b0 + NT_MESH_TRIANGLE_BLOCK : ntri;
+        for (int ti = b0; ti < b1; ++ti) {
+            const int* idx = a.indices + 3 * (size_t)(t0 + ti);
+            const int i0 = idx[0], i1 = idx[1], i2 = idx[2];
+            if ((unsigned)i0 >= (unsigned)nv || (unsigned)i1 >= (unsigned)nv || (unsigned)i2 >= (unsigned)nv) continue;
+            float t;
+            vec3 n;
+            if (rc_triangle(o, d, cw_mul(rc_ld3(a.vertices + 3 * (size_t)(v0 + i0)), s), cw_mul(rc_ld3(a.vertices + 3 * (size_t)(v0 + i1)), s),
+                            cw_mul(rc_ld3(a.vertices + 3 * (size_t)(v0 + i2)), s), t, n) &&
+                t >= 0.0f && t <= max_distance && t < bt) {
+                bt = t;
+                bn = n;
+            }
+        }
+    }
+    if (bt < RC_INF) rc_offer(best, max_distance, bt, id, k, bn);
+}
+
+NT_DI int rc_cell(float x, int n) {  // floor, clamped to the cells 0 .. n - 1
+    const float f = floorf(x);
+    return f < 0.0f ? 0 : (f > (float)(n - 1) ? n - 1 : (int)f);
+}
+
+// heightfield shape `id`: the ray clipped to the field's box, then one slab of the faster grid axis after the other
+NT_DI void rc_hfield(const nt_raycast_args& a, int id, int k, vec3 o, vec3 d, float max_distance, RcBest& best) {
+    const int hi_ = a.shape_heightfield_index[id];
+    if (hi_ < 0) return;
+    const nt_heightfield hd = a.heightfields[hi_];
+    const int ncx = hd.ncol - 1, ncy = hd.nrow - 1;
+    if (ncx <= 0 || ncy <= 0) return;
+    const float dx = 2.0f * hd.hx / (float)ncx, dy = 2.0f * hd.hy / (float)ncy, z_range = hd.max_z - hd.min_z;
+    const float* e = a.elevations + hd.data_offset;
+    const float eps = 1.0e-3f;  // in cells: far beyond the rounding of the cell coordinates, so that the walk never leaves out a hit
+    const float pad_z = eps * fabsf(z_range) + 1.0e-6f;
+    float t_a = 0.0f, t_b = max_distance;
+    if (!rc_clip(o, d, vec3(-hd.hx - eps * dx, -hd.hy - eps * dy, fminw(hd.min_z, hd.max_z) - pad_z),
+                 vec3(hd.hx + eps * dx, hd.hy + eps * dy, fmaxw(hd.min_z, hd.max_z) + pad_z), t_a, t_b))
+        return;
+    // cell coordinates along the ray: u(t) = u0 + du t (columns), v(t) = v0 + dv t (rows)
+    const float u0 = (o.x + hd.hx) / dx, du = d.x / dx, v0 = (o.y + hd.hy) / dy, dv = d.y / dy;
+    const bool major_u = fabsf(du) >= fabsf(dv);
+    const float m0 = major_u ? u0 : v0, dm = major_u ? du : dv, n0 = major_u ? v0 : u0, dn = major_u ? dv : du;
+    const int nm = major_u ? ncx : ncy, nn = major_u ? ncy : ncx;
+    float bt = RC_INF;
+    int btri = 0;
+    vec3 bn;
+    // (a ray that does not move along the grid, dm = 0: the one or two slabs it stands in)
+    const int i_first = rc_cell(m0 + dm * t_a - (dm < 0.0f ? -eps : eps), nm), i_last = rc_cell(m0 + dm * t_b + (dm < 0.0f ? -eps : eps), nm);
+    const int step = dm < 0.0f ? -1 : 1;
+    for (int i = i_first; step > 0 ? i <= i_last : i >= i_last; i += step) {
+        // the part of the ray inside slab i of the major axis
+        float s_in = t_a, s_out = t_b;
+        if (dm != 0.0f) {
+            const float ta = ((float)i - eps - m0) / dm, tb = ((float)(i + 1) + eps - m0) / dm;
+            s_in = fmaxw(s_in, fminw(ta, tb));
+            s_out = fminw(s_out, fmaxw(ta, tb));
+        }
+        if (s_in <= s_out) {
+            const float na = n0 + dn * s_in, nb = n0 + dn * s_out;
+            const int j0 = rc_cell(fminw(na, nb) - eps, nn), j1 = rc_cell(fmaxw(na, nb) + eps, nn);
+            for (int j = j0; j <= j1; ++j) {
+                const int col = major_u ? i : j, row = major_u ? j : i;
+                // get_triangle_shape_from_heightfield, as nt_mesh_triangle.hip builds the cell
+                const float x0 = -hd.hx + (float)col * dx, x1 = x0 + dx, y0 = -hd.hy + (float)row * dy, y1 = y0 + dy;
+                const float h00 = e[row * hd.ncol + col], h10 = e[row * hd.ncol + (col + 1)], h01 = e[(row + 1) * hd.ncol + col],
+                            h11 = e[(row + 1) * hd.ncol + (col + 1)];
+                const vec3 p00(x0, y0, hd.min_z + h00 * z_range), p10(x1, y0, hd.min_z + h10 * z_range), p01(x0, y1, hd.min_z + h01 * z_range),
+                    p11(x1, y1, hd.min_z + h11 * z_range);
+                for (int sub = 0; sub < 2; ++sub) {
+                    const int tri = (row * ncx + col) * 2 + sub;
+                    float t;
+                    vec3 n;
+                    if (rc_triangle(o, d, p00, sub == 0 ? p10 : p11, sub == 0 ? p11 : p01, t, n) && t >= 0.0f && t <= max_distance &&
+                        (t < bt || (t == bt && tri < btri))) {
+                        bt = t;
+                        btri = tri;
+                        bn = n;
+                    }
+                }
+            }
+            // a hit clearly before the end of this slab: no later slab holds a nearer one
+            if (dm != 0.0f && bt + 1.0e-4f * (1.0f + fabsf(s_out)) < s_out) break;
+        }
+    }
+    if (bt < RC_INF) rc_offer(best, max_distance, bt, id, k, bn);
+}
+
+__global__ void __launch_bounds__(RC_THREADS) raycast_kernel(nt_model m, const float* body_q, nt_raycast_args a, int wpb, int rl) {
+    extern __shared__ __align__(16) float lds[];
+    const int tid = threadIdx.x, K = a.target_count, R = a.ray_count;
+    const size_t ES = (size_t)m.env_stride;
+    const int groups = (m.env_count + wpb - 1) / wpb;
+    for (int g = blockIdx.x; g < groups; g += gridDim.x) {
+        __syncthreads();  // the previous group's records are no longer read
+        // stage: one (world, target) per lane
+        for (int item = tid; item < wpb * K; item += RC_THREADS) {
+            const int wl = item / K, k = item - wl * K, e = g * wpb + wl;
+            if (e >= m.env_count || (a.world_mask && !a.world_mask[e])) continue;
+            const int slot = a.targets[2 * k], type = a.targets[2 * k + 1];
+            float* rec = lds + (size_t)item * RC_REC;
+            int* irec = reinterpret_cast<int*>(rec);  // words 10, 11: type, Newton shape id
+            if (slot < 0 || slot >= m.ns + m.ng) { irec[10] = 0; irec[11] = -1; continue; }
+            float sp[10];
+            int id;
+            if (slot < m.ns) {
+                for (int c = 0; c < 10; ++c) sp[c] = m.shape_param[((size_t)c * m.ns + slot) * ES + e];
+                id = m.shape_local0 + e * m.ns + slot;
+            } else {
+                for (int c = 0; c < 10; ++c) sp[c] = m.gshape_param[(size_t)(slot - m.ns) * NT_SHAPE_PARAM_FLOATS + c];
+                id = m.gshape_id[slot - m.ns];
+            }
+            xform X(vec3(sp[0], sp[1], sp[2]), quat(sp[3], sp[4], sp[5], sp[6]));
+            const int body = m.shape_body[slot];
+            if (body >= 0 && body < m.nb) {
+                const float* q = body_q + (size_t)body * ES + e;
+                const size_t cs = (size_t)m.nb * ES;
+                X = xform(vec3(q[0], q[cs], q[2 * cs]), quat(q[3 * cs], q[4 * cs], q[5 * cs], q[6 * cs])) * X;
+            }
+            rec[0] = X.p.x; rec[1] = X.p.y; rec[2] = X.p.z;
+            rec[3] = X.q.x; rec[4] = X.q.y; rec[5] = X.q.z; rec[6] = X.q.w;
+            rec[7] = sp[7]; rec[8] = sp[8]; rec[9] = sp[9];
+            irec[10] = type;
+            irec[11] = id;
+        }
+        __syncthreads();
+        const int wl = tid / rl, e = g * wpb + wl;
+        if (e >= m.env_count || (a.world_mask && !a.world_mask[e])) continue;
+        const float* recs = lds + (size_t)wl * K * RC_REC;
+        for (int r = tid - wl * rl; r < R; r += rl) {
+            const size_t ray = a.rays_per_world ? (size_t)e * R + r : (size_t)r;
+            vec3 O = rc_ld3(a.origins + 3 * ray), D = rc_ld3(a.directions + 3 * ray);
+            const int rb = a.ray_body[r];
+            bool live = rb >= -1 && rb < m.nb;
+            if (rb >= 0 && live) {
+                const float* q = body_q + (size_t)rb * ES + e;
+                const size_t cs = (size_t)m.nb * ES;
+                const xform X(vec3(q[0], q[cs], q[2 * cs]), quat(q[3 * cs], q[4 * cs], q[5 * cs], q[6 * cs]));
+                O = xform_point(X, O);
+                D = quat_rotate(X.q, D);
+            }
+            const float len = length(D);
+            live = live && len > 0.0f;
+            RcBest best;
+            best.t = RC_INF; best.id = 0x7fffffff; best.k = -1;
+            if (live) {
+                D = D / len;
+                for (int k = 0; k < K; ++k) {  // primitives, ascending slot
+                    const float* rec = recs + (size_t)k * RC_REC;
+                    const int type = reinterpret_cast<const int*>(rec)[10];
+                    if (type == RC_MESH || type == RC_HFIELD || type == 0) continue;
+                    const quat q(rec[3], rec[4], rec[5], rec[6]);
+                    const vec3 o = quat_rotate_inv(q, O - vec3(rec[0], rec[1], rec[2])), d = quat_rotate_inv(q, D);
+                    float t;
+                    vec3 n;
+                    if (rc_primitive(type, vec3(rec[7], rec[8], rec[9]), o, d, t, n)) rc_offer(best, a.max_distance, t, reinterpret_cast<const int*>(rec)[11], k, n);
+                }
+                for (int k = 0; k < K; ++k) {  // meshes and heightfields, ascending slot
+                    const float* rec = recs + (size_t)k * RC_REC;
+                    const int type = reinterpret_cast<const int*>(rec)[10];
+                    if (type != RC_MESH && type != RC_HFIELD) continue;
+                    const quat q(rec[3], rec[4], rec[5], rec[6]);
+                    const vec3 o = quat_rotate_inv(q, O - vec3(rec[0], rec[1], rec[2])), d = quat_rotate_inv(q, D);
+                    if (type == RC_MESH) rc_mesh(a, reinterpret_cast<const int*>(rec)[11], k, vec3(rec[7], rec[8], rec[9]), o, d, a.max_distance, best);
+                    else rc_hfield(a, reinterpret_cast<const int*>(rec)[11], k, o, d, a.max_distance, best);
+                }
+            }
+            const size_t out = (size_t)e * R + r;
+            const bool hit = best.k >= 0;
+            a.distance[out] = hit ? best.t : -1.0f;
+            if (a.shape) a.shape[out] = hit ? best.id : -1;
+            if (a.normal) {
+                vec3 n;
+                if (hit) {
+                    const float* rec = recs + (size_t)best.k * RC_REC;
+                    n = quat_rotate(quat(rec[3], rec[4], rec[5], rec[6]), normalize(best.n));
+                }
+                a.normal[3 * out] = n.x; a.normal[3 * out + 1] = n.y; a.normal[3 * out + 2] = n.z;
+            }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" nt_status nt_mesh_plane_pairs(const nt_mesh_plane_args* a, void* stream) {
@@ -228,5 +648,47 @@ extern "C" nt_status nt_mesh_plane_pairs(const nt_mesh_plane_args* a, void* stre
 #endif
     if (blocks > grid_cap) blocks = grid_cap;
     hipLaunchKernelGGL(mesh_plane_pairs_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *a);
+    return hipGetLastError() == hipSuccess ? NT_OK : NT_ERR_LAUNCH;
+}
+
+extern "C" nt_status nt_raycast(const nt_model* m, const nt_state* s, const nt_raycast_args* a, void* stream) {
+    if (!m || !s || !a || !s->body_q || !a->origins || !a->directions || !a->ray_body || !a->distance || a->ray_count <= 0 ||
+        a->target_count < 0 || !(a->max_distance >= 0.0f) || m->env_count <= 0 || m->env_stride < m->env_count || m->nb <= 0 || m->ns < 0 || m->ng < 0)
+        return NT_ERR_INVALID_ARG;
+    const int K = a->target_count;
+    if (K > 0 && (!a->targets || !a->targets_host || !m->shape_body || (m->ns > 0 && !m->shape_param) || (m->ng > 0 && (!m->gshape_param || !m->gshape_id))))
+        return NT_ERR_INVALID_ARG;
+    bool mesh = false, hfield = false, unsupported = false;
+    for (int k = 0, prev = -1; k < K; ++k) {
+        const int slot = a->targets_host[2 * k], type = a->targets_host[2 * k + 1];
+        if (slot <= prev || slot >= m->ns + m->ng) return NT_ERR_INVALID_ARG;
+        prev = slot;
+        mesh = mesh || type == RC_MESH;
+        hfield = hfield || type == RC_HFIELD;
+        unsupported = unsupported || !(type == RC_PLANE || type == RC_HFIELD || type == RC_SPHERE || type == RC_CAPSULE || type == RC_ELLIPSOID ||
+                                       type == RC_CYLINDER || type == RC_BOX || type == RC_MESH || type == RC_CONE);
+    }
+    if (mesh && (!a->shape_vertex_range || !a->shape_triangle_range || !a->vertices || !a->indices)) return NT_ERR_INVALID_ARG;
+    if ((a->block_bounds != nullptr) != (a->shape_block_start != nullptr)) return NT_ERR_INVALID_ARG;
+    if (hfield && (!a->shape_heightfield_index || !a->heightfields || !a->elevations)) return NT_ERR_INVALID_ARG;
+    if (unsupported) return NT_ERR_UNSUPPORTED;
+    // worlds per workgroup: four / two while the rays of a world leave lanes idle and the staged targets still fit the CU
+    int wpb = a->ray_count <= 64 ? 4 : (a->ray_count <= 128 ? 2 : 1);
+    const size_t per_world = (size_t)K * RC_REC * sizeof(float);
+    while (wpb > 1 && wpb * per_world > RC_LDS_BYTES_PER_CU) wpb /= 2;
+    if (per_world > RC_LDS_BYTES_PER_CU) return NT_ERR_UNSUPPORTED;
+    const size_t lds_bytes = wpb * per_world > 16 ? wpb * per_world : 16;
+#ifdef NT_EMULATED_GRID
+    const long long grid_cap = NT_EMULATED_GRID;
+#else
+    const long long grid_cap = 8192;
+#endif
+    long long blocks = ((long long)m->env_count + wpb - 1) / wpb;
+    if (blocks > grid_cap) blocks = grid_cap;
+    if (lds_bytes > 48 * 1024 &&
+        hipFuncSetAttribute((const void*)raycast_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
+        return NT_ERR_LAUNCH;
+    hipLaunchKernelGGL(raycast_kernel, dim3((unsigned)blocks), dim3(RC_THREADS), lds_bytes, (hipStream_t)stream, *m, (const float*)s->body_q, *a, wpb,
+                       RC_THREADS / wpb);
     return hipGetLastError() == hipSuccess ? NT_OK : NT_ERR_LAUNCH;
 }

@@ -1,0 +1,437 @@
+"""Ray-cast sensors: ``SensorRaycast`` casts R rays per world against the shapes of that world -- a height scan under a robot's base,
+a lidar sweep over the other bodies.  The capability of the reference's ``newton.sensors.SensorRaycast``; that one is a single
+camera, this one is ONE SENSOR PER WORLD of the replicated model, because that is what the batched layout serves: the same R rays
+(or R rays of its own) in every world, attached to a body of that world or fixed in the world frame.
+
+On a GPU model ``SensorRaycast.eval`` is one launch of raycast_kernel (nt_raycast, include/newton_hip_mesh.h -- the contract is written
+there): no allocation, no synchronisation, recordable by ``newton_amd.graph.capture``; the rays are read through resident pointers,
+so ``set_rays`` followed by a replay takes effect.  On a host model the same contract runs in numpy, float64 inside, vectorised over
+worlds and rays, every triangle of a mesh / heightfield tested (no block skip, no grid walk); that path is the reference the kernel is
+tested against."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from .articulation import _host_array, _qinv, _qmul, _qrot
+from .enums import GeoType
+
+RAY_TARGET_TYPES = (GeoType.PLANE, GeoType.HFIELD, GeoType.SPHERE, GeoType.CAPSULE, GeoType.ELLIPSOID, GeoType.CYLINDER, GeoType.BOX, GeoType.MESH,
+                    GeoType.CONE)
+_PAIR_CHUNK = 1 << 19  # (ray, triangle) pairs per batch of the host path's triangle tests (bounds its memory)
+
+
+def _dot(a, b):
+    return np.sum(a * b, axis=-1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the float64 host mathematics (the reference of the kernel).  Every routine takes the ray in the shape frame, o / d [N, 3], and returns
+# (hit [N] bool, t [N], n [N, 3]): the entering point of the surface that faces the ray, its normal unnormalised in the shape frame
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _sphere(o, d, r):
+    a = _dot(d, d)
+    t0 = -_dot(o, d) / a
+    c = o + d * t0[:, None]
+    disc = r * r - _dot(c, c)
+    ok = disc > 0.0
+    h = np.sqrt(np.where(ok, disc, 0.0) / a)
+    return ok, t0 - h, c - d * h[:, None]
+
+
+def _lateral(o, d, r):
+    """Entering root on the infinite cylinder about z: (root exists, parallel and inside, t)."""
+    a = d[:, 0] ** 2 + d[:, 1] ** 2
+    par = ~(a > 0.0)
+    a_ = np.where(par, 1.0, a)
+    t0 = -(o[:, 0] * d[:, 0] + o[:, 1] * d[:, 1]) / a_
+    cx, cy = o[:, 0] + d[:, 0] * t0, o[:, 1] + d[:, 1] * t0
+    disc = r * r - (cx * cx + cy * cy)
+    root = ~par & (disc > 0.0)
+    t = t0 - np.sqrt(np.where(root, disc, 0.0) / a_)
+    return root, par & (o[:, 0] ** 2 + o[:, 1] ** 2 < r * r), t
+
+
+def _capped(o, d, r, hh, round_ends):
+    root, inside, tl = _lateral(o, d, r)
+    z = o[:, 2] + d[:, 2] * tl
+    lat = root & (np.abs(z) <= hh)
+    end = np.where(root, np.where(z > 0.0, hh, -hh), np.where(d[:, 2] < 0.0, hh, -hh))
+    need = (root & ~lat) | inside
+    n_lat = np.stack([o[:, 0] + d[:, 0] * tl, o[:, 1] + d[:, 1] * tl, np.zeros_like(tl)], axis=1)
+    if round_ends:  # capsule: the hemisphere of that end
+        oc = o.copy()
+        oc[:, 2] -= end
+        ok, ts, p = _sphere(oc, d, r)
+        cap = need & ok & ~(p[:, 2] * end < 0.0)
+        n_cap = p
+    else:  # cylinder: the cap disc
+        facing = d[:, 2] * end < 0.0
+        ts = (end - o[:, 2]) / np.where(facing, d[:, 2], 1.0)
+        x, y = o[:, 0] + d[:, 0] * ts, o[:, 1] + d[:, 1] * ts
+        cap = need & facing & (x * x + y * y <= r * r)
+        n_cap = np.stack([np.zeros_like(ts), np.zeros_like(ts), end], axis=1)
+    return lat | cap, np.where(lat, tl, ts), np.where(lat[:, None], n_lat, n_cap)
+
+
+def _box(o, d, half):
+    t0 = -_dot(o, d) / _dot(d, d)
+    c = o + d * t0[:, None]
+    nz = d != 0.0
+    d_ = np.where(nz, d, 1.0)
+    ta, tb = (-half - c) / d_, (half - c) / d_
+    tn = np.where(nz, np.minimum(ta, tb), -np.inf)
+    tf = np.where(nz, np.maximum(ta, tb), np.inf)
+    miss = np.any(~nz & (np.abs(c) > half), axis=1)
+    axis = np.argmax(tn, axis=1)  # (the first axis on a tie)
+    t_in, t_out = tn.max(axis=1), tf.min(axis=1)
+    n = np.zeros_like(o)
+    rows = np.arange(len(o))
+    n[rows, axis] = np.where(d[rows, axis] > 0.0, -1.0, 1.0)
+    return ~miss & (t_in < t_out), t0 + t_in, n
+
+
+def _cone(o, d, r, hh):
+    t0 = -_dot(o, d) / _dot(d, d)
+    c = o + d * t0[:, None]
+    k = np.where(hh > 0.0, r / np.where(hh > 0.0, 2.0 * hh, 1.0), 0.0)
+    k2 = k * k
+    w0 = hh - c[:, 2]
+    A = d[:, 0] ** 2 + d[:, 1] ** 2 - k2 * d[:, 2] ** 2
+    B = c[:, 0] * d[:, 0] + c[:, 1] * d[:, 1] + k2 * w0 * d[:, 2]
+    Cc = c[:, 0] ** 2 + c[:, 1] ** 2 - k2 * w0 * w0
+    disc = B * B - A * Cc
+    q = -(B + np.where(B < 0.0, -1.0, 1.0) * np.sqrt(np.where(disc >= 0.0, disc, 0.0)))
+    best = np.full(len(o), np.inf)
+    bn = np.zeros_like(o)
+    for num, den in ((q, A), (Cc, q)):
+        ok = (disc >= 0.0) & (den != 0.0)
+        tr = num / np.where(den != 0.0, den, 1.0)
+        w = w0 - tr * d[:, 2]
+        nn = np.stack([c[:, 0] + d[:, 0] * tr, c[:, 1] + d[:, 1] * tr, k2 * w], axis=1)
+        ok = ok & (w > 0.0) & (w <= 2.0 * hh) & (_dot(nn, d) < 0.0) & (tr < best)
+        best = np.where(ok, tr, best)
+        bn = np.where(ok[:, None], nn, bn)
+    up = d[:, 2] > 0.0  # the base disc, facing -z
+    tr = (-hh - c[:, 2]) / np.where(up, d[:, 2], 1.0)
+    x, y = c[:, 0] + d[:, 0] * tr, c[:, 1] + d[:, 1] * tr
+    ok = up & (x * x + y * y <= r * r) & (tr < best)
+    best = np.where(ok, tr, best)
+    bn = np.where(ok[:, None], np.array([0.0, 0.0, -1.0]), bn)
+    return best < np.inf, t0 + best, bn
+
+
+def _plane(o, d, s):
+    facing = d[:, 2] < 0.0
+    t = -o[:, 2] / np.where(facing, d[:, 2], 1.0)
+    finite = (s[:, 0] != 0.0) | (s[:, 1] != 0.0)
+    x, y = o[:, 0] + d[:, 0] * t, o[:, 1] + d[:, 1] * t
+    inside = ~finite | ((np.abs(x) <= s[:, 0]) & (np.abs(y) <= s[:, 1]))
+    return facing & inside, t, np.broadcast_to(np.array([0.0, 0.0, 1.0]), o.shape).copy()
+
+
+def _primitive(gtype, s, o, d):
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        if gtype == GeoType.PLANE:
+            return _plane(o, d, s)
+        if gtype in (GeoType.SPHERE, GeoType.ELLIPSOID):
+            rad = np.repeat(s[:, :1], 3, axis=1) if gtype == GeoType.SPHERE else s
+            ok, t, p = _sphere(o / rad, d / rad, 1.0)
+            return ok, t, p / rad
+        if gtype == GeoType.BOX:
+            return _box(o, d, s)
+        if gtype == GeoType.CAPSULE:
+            return _capped(o, d, s[:, 0], s[:, 1], True)
+        if gtype == GeoType.CYLINDER:
+            return _capped(o, d, s[:, 0], s[:, 1], False)
+        if gtype == GeoType.CONE:
+            return _cone(o, d, s[:, 0], s[:, 1])
+    raise NotImplementedError(f"no ray test for {GeoType(gtype).name}")
+
+
+def _triangles(o, d, v0, v1, v2, s, max_distance):
+    """Moeller-Trumbore of every ray against every triangle (vertices [T, 3] times the ray's scale s [N, 3]), front faces only:
+    (hit, t, n) of the nearest, the lower triangle index on a tie."""
+    N = len(o)
+    hit, t_out, n_out = np.zeros(N, bool), np.full(N, np.inf), np.zeros((N, 3))
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        chunk = max(1, _PAIR_CHUNK // max(len(v0), 1))
+        for c0 in range(0, N, chunk):
+            sl = slice(c0, min(c0 + chunk, N))
+            oo, dd, ss = o[sl, None, :], d[sl, None, :], s[sl, None, :]
+            a0, a1, a2 = v0[None] * ss, v1[None] * ss, v2[None] * ss
+            e1, e2 = a1 - a0, a2 - a0
+            pvec = np.cross(dd, e2)
+            det = _dot(e1, pvec)
+            tvec = oo - a0
+            u = _dot(tvec, pvec)
+            qvec = np.cross(tvec, e1)
+            v = _dot(dd, qvec)
+            t = _dot(e2, qvec) / np.where(det > 0.0, det, 1.0)
+            ok = (det > 0.0) & (u >= 0.0) & (u <= det) & (v >= 0.0) & (u + v <= det) & (t >= 0.0) & (t <= max_distance)
+            t = np.where(ok, t, np.inf)
+            k = np.argmin(t, axis=1)  # (the first of equal minima: the lower index)
+            rows = np.arange(t.shape[0])
+            hit[sl], t_out[sl] = ok[rows, k], t[rows, k]
+            n_out[sl] = np.cross(e1[rows, k], e2[rows, k])
+    return hit, t_out, n_out
+
+
+def _heightfield_triangles(model, h):
+    """The two triangles per cell of heightfield h, vertices in float64 from the float32 record, in the triangle leg's index order."""
+    off, nrow, ncol, hx, hy, zlo, zhi = model.heightfield_data[h]
+    hx, hy, zlo, zhi = (float(np.float32(x)) for x in (hx, hy, zlo, zhi))
+    e = np.asarray(model.heightfield_elevations, dtype=np.float64)[off:off + nrow * ncol].reshape(nrow, ncol)
+    dx, dy = 2.0 * hx / (ncol - 1), 2.0 * hy / (nrow - 1)
+    x0 = -hx + np.arange(ncol - 1) * dx
+    y0 = -hy + np.arange(nrow - 1) * dy
+    X0, Y0 = np.meshgrid(x0, y0)  # [row, col]
+    z = zlo + e * (zhi - zlo)
+    p00 = np.stack([X0, Y0, z[:-1, :-1]], axis=-1)
+    p10 = np.stack([X0 + dx, Y0, z[:-1, 1:]], axis=-1)
+    p01 = np.stack([X0, Y0 + dy, z[1:, :-1]], axis=-1)
+    p11 = np.stack([X0 + dx, Y0 + dy, z[1:, 1:]], axis=-1)
+    v0 = np.stack([p00, p00], axis=2).reshape(-1, 3)
+    v1 = np.stack([p10, p11], axis=2).reshape(-1, 3)
+    v2 = np.stack([p11, p01], axis=2).reshape(-1, 3)
+    return v0, v1, v2
+
+
+def raycast_numpy(model, body_q, origins, directions, ray_body, max_distance, slots, world_mask=None):
+    """The contract of nt_raycast in float64: (distance [E, R], normal [E, R, 3], shape [E, R] int32).  body_q [E * nb, 7]; origins /
+    directions [R, 3] or [E, R, 3]; ray_body [R]; slots: the selected shape slots (env-local shapes, then global shapes).  Rows of
+    worlds outside world_mask are returned as misses."""
+    t = model.env
+    E, nb, ns = t.env_count, t.nb, t.ns
+    bq = np.asarray(_host_array(body_q), dtype=np.float64).reshape(E, nb, 7)
+    rb = np.asarray(ray_body, dtype=np.int64).reshape(-1)
+    R = len(rb)
+    o = np.broadcast_to(np.asarray(_host_array(origins), dtype=np.float64).reshape(-1, R, 3), (E, R, 3))
+    d = np.broadcast_to(np.asarray(_host_array(directions), dtype=np.float64).reshape(-1, R, 3), (E, R, 3))
+    live = (rb >= -1) & (rb < nb)
+    attached = live & (rb >= 0)
+    X = bq[:, np.where(attached, rb, 0), :]  # [E, R, 7]
+    O = np.where(attached[None, :, None], X[..., :3] + _qrot(X[..., 3:], o), o).reshape(-1, 3)
+    D = np.where(attached[None, :, None], _qrot(X[..., 3:], d), d).reshape(-1, 3)
+    length = np.linalg.norm(D, axis=1)
+    live = np.repeat(live[None, :], E, axis=0).reshape(-1) & (length > 0.0)
+    if world_mask is not None:
+        live = live & np.repeat(np.asarray(_host_array(world_mask)).astype(bool).reshape(E), R)
+    D = D / np.where(length > 0.0, length, 1.0)[:, None]
+    N = E * R
+    best_t, best_id, best_n = np.full(N, np.inf), np.full(N, np.iinfo(np.int64).max), np.zeros((N, 3))
+    xf = np.asarray(model.shape_transform, dtype=np.float64).reshape(-1, 7)
+    sc = np.asarray(model.shape_scale, dtype=np.float64).reshape(-1, 3)
+    for slot in slots:
+        slot = int(slot)
+        ids = t.shape_local0 + np.arange(E) * ns + slot if slot < ns else np.full(E, int(t.gshape_id[slot - ns]))
+        gtype, body = int(t.shape_type[slot]), int(t.shape_body[slot])
+        Xs = xf[ids]
+        if body >= 0:
+            Xb = bq[:, body]
+            Xs = np.concatenate([Xb[:, :3] + _qrot(Xb[:, 3:], Xs[:, :3]), _qmul(Xb[:, 3:], Xs[:, 3:])], axis=1)
+        Xs, s, rid = np.repeat(Xs, R, axis=0), np.repeat(sc[ids], R, axis=0), np.repeat(ids, R)
+        qi = _qinv(Xs[:, 3:])
+        ol, dl = _qrot(qi, O - Xs[:, :3]), _qrot(qi, D)
+        if gtype == GeoType.MESH:
+            i0 = int(ids[0])
+            (vs, nv), (ts, nt) = model.mesh_vertex_range[i0], model.mesh_triangle_range[i0]
+            V = np.asarray(model.mesh_vertices, dtype=np.float64)[vs:vs + nv]
+            tri = np.asarray(model.mesh_indices)[ts:ts + nt]
+            hit, tt, n = _triangles(ol, dl, V[tri[:, 0]], V[tri[:, 1]], V[tri[:, 2]], s, max_distance)
+        elif gtype == GeoType.HFIELD:
+            v0, v1, v2 = _heightfield_triangles(model, int(model.shape_heightfield_index[int(ids[0])]))
+            hit, tt, n = _triangles(ol, dl, v0, v1, v2, np.ones_like(s), max_distance)
+        else:
+            hit, tt, n = _primitive(gtype, s, ol, dl)
+        with np.errstate(invalid="ignore"):
+            take = live & hit & (tt >= 0.0) & (tt <= max_distance) & ((tt < best_t) | ((tt == best_t) & (rid < best_id)))
+        nw = _qrot(Xs[:, 3:], n / np.where(take, np.linalg.norm(n, axis=1), 1.0)[:, None])
+        best_t, best_id = np.where(take, tt, best_t), np.where(take, rid, best_id)
+        best_n = np.where(take[:, None], nw, best_n)
+    hit = best_t < np.inf
+    return (np.where(hit, best_t, -1.0).reshape(E, R), np.where(hit[:, None], best_n, 0.0).reshape(E, R, 3),
+            np.where(hit, best_id, -1).astype(np.int32).reshape(E, R))
+
+
+class SensorRaycast:
+    """R rays per world, cast at the shapes of that world (see the module text: one sensor per world, not one camera).
+
+    ``origins`` / ``directions``: [R, 3] (one pattern shared by every world) or [world, R, 3]; ``ray_body``: an int or [R], the
+    env-local body a ray is attached to, -1 for the world frame.  ``shape_mask``: bool per shape slot of a world (its env-local shapes,
+    then the global shapes), default every slot; ``exclude_bodies`` removes the shapes carried by those env-local bodies (a lidar on
+    the robot ignores the robot).  Only surfaces facing the ray are hit, the nearest within ``max_distance`` wins.
+
+    ``eval(state)`` fills ``distance`` [world, R] (-1: miss), ``normal`` [world, R, 3] (unit, world frame; zeros on a miss) and
+    ``shape`` [world, R] (Newton shape id, -1 on a miss): resident float32 / int32 tensors on a GPU model, float64 / int32 numpy
+    arrays on a host model.  Refused with NotImplementedError: heterogeneous models, and a mask that selects a CONVEX_MESH, a
+    GAUSSIAN or a barrel cylinder (they are named)."""
+
+    def __init__(self, model, origins, directions, ray_body=-1, max_distance=1e3, shape_mask=None, exclude_bodies=(), want_normal=True,
+                 want_shape=True):
+        if getattr(model, "is_heterogeneous", False):
+            raise NotImplementedError("SensorRaycast: heterogeneous models are unsupported (one sensor is R rays in every world of a replicated model)")
+        t = model.env
+        E, nslot = t.env_count, t.ns + t.ng
+        self.model, self.max_distance = model, float(max_distance)
+        if not self.max_distance >= 0.0:
+            raise ValueError("max_distance must be >= 0")
+        o = np.asarray(_host_array(origins), dtype=np.float32)
+        d = np.asarray(_host_array(directions), dtype=np.float32)
+        if o.shape != d.shape or o.ndim not in (2, 3) or o.shape[-1] != 3 or o.shape[-2] == 0 or (o.ndim == 3 and o.shape[0] != E):
+            raise ValueError(f"origins / directions must both have shape [R, 3] or [{E}, R, 3]")
+        self.ray_count, self.rays_per_world = int(o.shape[-2]), o.ndim == 3
+        rb = np.asarray(ray_body, dtype=np.int32).reshape(-1)
+        rb = np.full(self.ray_count, rb[0], np.int32) if rb.size == 1 else rb
+        if rb.shape != (self.ray_count,) or np.any(rb < -1) or np.any(rb >= t.nb):
+            raise ValueError(f"ray_body must be an int or [R] of env-local body indices (-1 .. {t.nb - 1})")
+        self.ray_body = rb
+        mask = np.ones(nslot, bool) if shape_mask is None else np.asarray(_host_array(shape_mask)).astype(bool).reshape(-1)
+        if mask.shape != (nslot,):
+            raise ValueError(f"shape_mask must have {nslot} entries (env-local shapes, then global shapes)")
+        excluded = [int(b) for b in exclude_bodies]
+        if any(not 0 <= b < t.nb for b in excluded):
+            raise ValueError(f"exclude_bodies: env-local body indices 0 .. {t.nb - 1}")
+        self.shape_mask = mask & ~np.isin(np.asarray(t.shape_body), excluded)
+        self.slots = np.flatnonzero(self.shape_mask).astype(np.int32)
+        self._check_targets()
+        R = self.ray_count
+        self._gpu = bool(getattr(model, "is_gpu", False))
+        if self._gpu:
+            self._init_device(o, d, want_normal, want_shape)
+        else:
+            self.origins, self.directions = o.copy(), d.copy()
+            self.distance = np.full((E, R), -1.0)
+            self.normal = np.zeros((E, R, 3)) if want_normal else None
+            self.shape = np.full((E, R), -1, np.int32) if want_shape else None
+
+    def _check_targets(self):
+        model, t = self.model, self.model.env
+        scale = np.asarray(model.shape_scale).reshape(-1, 3)
+        bad = []
+        for slot in self.slots:
+            gtype = int(t.shape_type[slot])
+            ids = t.shape_local0 + np.arange(t.env_count) * t.ns + slot if slot < t.ns else np.array([int(t.gshape_id[slot - t.ns])])
+            if gtype not in [int(g) for g in RAY_TARGET_TYPES]:
+                bad.append(f"slot {int(slot)} (shape {int(ids[0])}): {GeoType(gtype).name}")
+            elif gtype == GeoType.CYLINDER and np.any(scale[ids, 2] != 0.0):
+                bad.append(f"slot {int(slot)} (shape {int(ids[0])}): barrel CYLINDER")
+        if bad:
+            raise NotImplementedError("SensorRaycast: these shapes are no ray targets, take them out of shape_mask -- " + "; ".join(bad))
+
+    # -----------------------------------------------------------------------------------------------------------------------------
+    def _init_device(self, o, d, want_normal, want_shape):
+        import torch  # noqa: PLC0415
+
+        from . import _lib  # noqa: PLC0415
+
+        model, t = self.model, self.model.env
+        dm = model.device_model()
+        dev = dm.device
+        E, R = t.env_count, self.ray_count
+        self._keep = []
+
+        def up(a, dtype):
+            x = torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
+            if x.numel() == 0:
+                x = torch.zeros(1, dtype=x.dtype, device=dev)
+            self._keep.append(x)
+            return x
+
+        self.origins, self.directions = up(o, np.float32), up(d, np.float32)
+        self._ray_body = up(self.ray_body, np.int32)
+        self.distance = torch.full((E, R), -1.0, dtype=torch.float32, device=dev)
+        self.normal = torch.zeros((E, R, 3), dtype=torch.float32, device=dev) if want_normal else None
+        self.shape = torch.full((E, R), -1, dtype=torch.int32, device=dev) if want_shape else None
+        self._world_mask = torch.ones(E, dtype=torch.uint8, device=dev)
+        types = np.asarray(t.shape_type)[self.slots]
+        self._targets_host = np.ascontiguousarray(np.stack([self.slots, types], axis=1), dtype=np.int32).reshape(-1, 2)
+        a = _lib.nt_raycast_args()
+        a.ray_count, a.rays_per_world = R, int(self.rays_per_world)
+        a.origins, a.directions, a.ray_body = self.origins.data_ptr(), self.directions.data_ptr(), self._ray_body.data_ptr()
+        a.max_distance, a.target_count = self.max_distance, len(self.slots)
+        a.targets, a.targets_host = up(self._targets_host, np.int32).data_ptr(), self._targets_host.ctypes.data
+        a.distance = self.distance.data_ptr()
+        a.normal = None if self.normal is None else self.normal.data_ptr()
+        a.shape = None if self.shape is None else self.shape.data_ptr()
+        # The sensor uploads its own mesh / heightfield tables: the copies of sdf_pipeline.SdfLeg exist only for models whose pairs take
+        # those legs, and belong to a CollisionPipeline the sensor may never see.
+        if np.any(types == int(GeoType.MESH)):
+            from .mesh import triangle_block_bounds  # noqa: PLC0415
+
+            vr, tr = np.asarray(model.mesh_vertex_range).reshape(-1, 2), np.asarray(model.mesh_triangle_range).reshape(-1, 2)
+            blk_start, blk_of, tables, n_blk = np.zeros(len(vr), np.int32), {}, [], 0
+            for i in range(len(vr)):  # one table per distinct mesh, as in sdf_pipeline.SdfLeg
+                if tr[i, 1] <= 0:
+                    continue
+                key = (int(vr[i, 0]), int(tr[i, 0]), int(tr[i, 1]))
+                if key not in blk_of:
+                    blk_of[key] = n_blk
+                    tables.append(triangle_block_bounds(np.asarray(model.mesh_vertices)[vr[i, 0]:vr[i, 0] + vr[i, 1]],
+                                                        np.asarray(model.mesh_indices)[tr[i, 0]:tr[i, 0] + tr[i, 1]]))
+                    n_blk += len(tables[-1])
+                blk_start[i] = blk_of[key]
+            a.shape_vertex_range, a.shape_triangle_range = up(vr, np.int32).data_ptr(), up(tr, np.int32).data_ptr()
+            a.vertices, a.indices = up(model.mesh_vertices, np.float32).data_ptr(), up(model.mesh_indices, np.int32).data_ptr()
+            a.block_bounds, a.shape_block_start = up(np.concatenate(tables), np.float32).data_ptr(), up(blk_start, np.int32).data_ptr()
+        if np.any(types == int(GeoType.HFIELD)):
+            hf = (_lib.nt_heightfield * model.heightfield_count)()
+            for k, (off, nrow, ncol, hx, hy, zlo, zhi) in enumerate(model.heightfield_data):
+                hf[k] = _lib.nt_heightfield(int(off), int(nrow), int(ncol), float(hx), float(hy), float(zlo), float(zhi))
+            a.shape_heightfield_index = up(model.shape_heightfield_index, np.int32).data_ptr()
+            a.heightfields = up(np.frombuffer(bytes(hf), dtype=np.uint8).copy(), np.uint8).data_ptr()
+            a.elevations = up(model.heightfield_elevations, np.float32).data_ptr()
+        self._args = a
+
+    # -----------------------------------------------------------------------------------------------------------------------------
+    def set_rays(self, origins, directions):
+        """New origins / directions of the same shape, copied into the resident arrays (a captured graph sees them on its next replay)."""
+        for dst, src, what in ((self.origins, origins, "origins"), (self.directions, directions, "directions")):
+            if hasattr(dst, "copy_"):
+                import torch  # noqa: PLC0415
+
+                x = src if hasattr(src, "data_ptr") else torch.from_numpy(np.ascontiguousarray(_host_array(src), dtype=np.float32))
+                if tuple(x.shape) != tuple(dst.shape):
+                    raise ValueError(f"{what} must have shape {tuple(dst.shape)}")
+                dst.copy_(x)
+            else:
+                x = np.asarray(_host_array(src), dtype=np.float32)
+                if x.shape != dst.shape:
+                    raise ValueError(f"{what} must have shape {dst.shape}")
+                dst[...] = x
+
+    def eval(self, state, world_mask=None):
+        """Cast from ``state.body_q``.  ``world_mask`` ([world] bool): the rows of unselected worlds are neither computed nor written.
+        GPU model: one kernel launch on the model's stream (the mask is copied into a resident buffer first)."""
+        t = self.model.env
+        if world_mask is not None and int(np.prod(np.shape(world_mask))) != t.env_count:
+            raise ValueError(f"world_mask must have {t.env_count} entries")
+        if self._gpu:
+            from . import _lib  # noqa: PLC0415
+            from .state import State  # noqa: PLC0415
+
+            if not isinstance(state, State):
+                raise TypeError("SensorRaycast.eval: a GPU model needs a State (body_q is read on the device)")
+            dm = self.model.device_model()
+            if world_mask is not None:
+                import torch  # noqa: PLC0415
+
+                wm = world_mask if hasattr(world_mask, "data_ptr") else torch.from_numpy(np.asarray(world_mask).astype(np.uint8))
+                self._world_mask.copy_(wm.reshape(-1).to(torch.uint8))
+            self._args.world_mask = None if world_mask is None else self._world_mask.data_ptr()
+            d = state._desc()
+            st = dm.lib.nt_raycast(C.byref(dm.desc), C.byref(d), C.byref(self._args), dm.stream())
+            if st == -3:  # NT_ERR_UNSUPPORTED
+                raise NotImplementedError("SensorRaycast.eval: nt_raycast answered NT_ERR_UNSUPPORTED (the selected shapes of one world do "
+                                          "not fit the LDS, or a shape type is no ray target)")
+            _lib.check(st, "nt_raycast")
+            return
+        dist, normal, shape = raycast_numpy(self.model, state.body_q, self.origins, self.directions, self.ray_body, self.max_distance, self.slots,
+                                            world_mask)
+        sel = slice(None) if world_mask is None else np.asarray(_host_array(world_mask)).astype(bool).reshape(-1)
+        self.distance[sel] = dist[sel]
+        if self.normal is not None:
+            self.normal[sel] = normal[sel]
+        if self.shape is not None:
+            self.shape[sel] = shape[sel]
