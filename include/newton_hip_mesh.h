@@ -146,7 +146,8 @@ nt_status nt_mesh_triangle_pairs(const nt_mesh_triangle_args* args, void* stream
  *              (t is unchanged), the ray moved to its point nearest the centre first, disc = 1 - |c|^2 > 0 (a tangent ray misses);
  *              n = normalize(p_unit / radii), the inverse-transpose scale.
  *   BOX        half extents scale xyz: slab test from the ray's point nearest the centre, n = the entered face (first axis on a tie);
- *              needs t_enter < t_exit.
+ *              needs t_enter < t_exit, and |c| < half extent on an axis with a zero direction component: a ray that only touches
+ *              the box (through an edge, or inside a face plane) misses, like the tangent to a sphere.
  *   CAPSULE    radius scale x, half height scale y along z (nt_primitives.hpp / nt_convex.hpp): the entering root on the infinite
  *              cylinder (2-D, from the point nearest the axis); |z| <= half height there: the lateral surface, else the hemisphere
  *              of that end.  A ray parallel to the axis takes the hemisphere it runs towards.

@@ -307,6 +307,7 @@ NT_DI bool rc_cylinder(vec3 o, vec3 d, float r, float hh, float& t, vec3& n) {
     return true;
 }
 
+// (a ray that only touches the box misses it, like a tangent to the sphere: t_in < t_out, and |c| < half on an axis it does not move along)
 NT_DI bool rc_box(vec3 o, vec3 d, vec3 half, float& t, vec3& n) {
     const float t0 = -dot(o, d) / dot(d, d);
     const vec3 c = o + d * t0;
@@ -318,7 +319,7 @@ NT_DI bool rc_box(vec3 o, vec3 d, vec3 half, float& t, vec3& n) {
         const float tn = fminw(ta, tb), tf = fmaxw(ta, tb);   \
         if (tn > t_in) { t_in = tn; axis = (I); }             \
         t_out = fminw(t_out, tf);                             \
-    } else if (fabsf(C) > (H)) {                              \
+    } else if (fabsf(C) >= (H)) {                             \
         return false;                                         \
     }
     RC_SLAB(0, c.x, d.x, half.x)

@@ -83,7 +83,7 @@ def _box(o, d, half):
     ta, tb = (-half - c) / d_, (half - c) / d_
     tn = np.where(nz, np.minimum(ta, tb), -np.inf)
     tf = np.where(nz, np.maximum(ta, tb), np.inf)
-    miss = np.any(~nz & (np.abs(c) > half), axis=1)
+    miss = np.any(~nz & (np.abs(c) >= half), axis=1)  # (a ray in a face plane touches the box, it does not enter it: a miss)
     axis = np.argmax(tn, axis=1)  # (the first axis on a tie)
     t_in, t_out = tn.max(axis=1), tf.min(axis=1)
     n = np.zeros_like(o)
