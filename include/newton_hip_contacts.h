@@ -136,6 +136,60 @@ nt_status nt_contacts_match_report_groups(int32_t group_count, const nt_contact_
 nt_status nt_contacts_order_save_groups(int32_t group_count, const nt_contact_group* groups, const nt_sorted_contacts* sorted,
                                         const nt_contact_report* r, void* stream);
 
+/* ---- contact sensor: net contact force per world on chosen sets of shapes, split by counterpart -------------------------------------
+ * (newton_amd.sensors.SensorContact; reference capability: newton.sensors.SensorContact.)  One launch of contact_sensor_kernel straight
+ * from the slot-major contacts and the rows of nt_contacts.flat, after an nt_xpbd_step that reported its impulses
+ * (nt_xpbd_report.contact_impulse, nt_flat_rows.impulse): no export, no allocation, no synchronisation, no host read.
+ *
+ * Sensing objects and counterparts.  Per world there are S sensing objects and C counterparts, each a set of shape slots of a world
+ * (ns env-local slots, then ng global shapes): slot_sensing[slot] in -1 .. S-1, slot_counterpart[slot] in -1 .. C-1.  A slot belongs to
+ * at most one sensing object and at most one counterpart (that is what a table per slot can say); it may be both.
+ *
+ * Output.  net_force [env_count][S][include_total + C][3]: column 0 (with include_total) is the sum over every contact of the sensing
+ * object, column include_total + c the part exchanged with counterpart c; the value is the force ON the sensing object.
+ *
+ * One contact contributes f = impulse[0:3] * (1.0f / dt), the expression of nt_contacts_export_force (a contribution equals the linear
+ * part of that contact's Contacts.force row bit for bit): +f to the sensing object of shape0 (Contacts.force is the force on shape0's
+ * body), -f to the sensing object of shape1; a counterpart column takes it when the OTHER shape of the contact is in that counterpart.
+ * Both shapes may be sensing objects: each side gets its contribution, and when both lie in the same sensing object the cell takes +f,
+ * then -f.  Skipped: slots with shape0 < 0 (unused), rows with shape0 == shape1 (inert, both -1), shape ids that are no shape of the
+ * world (no env-local id of that world, no global id).
+ *
+ * Summation order, fixed: every cell is a float32 sequential sum from 0.0f over the world's slots in ascending slot index, then (when
+ * nt_contacts.flat carries row_start / shape0 / shape1 / impulse and row_capacity > 0) over the world's rows
+ * [row_start[w], row_start[w + 1]), clamped to min(row_start[env_count], row_capacity), in ascending row index.  No float atomics, no
+ * grouping that depends on the launch shape (one lane owns a cell from its first contact to its last).  Hence:
+ *   - replicated worlds give equal bits;
+ *   - with the raw (non-deterministic) export order, a cell equals the float32 sequential sum over that world's entries of the flat
+ *     Contacts.force / rigid_contact_shape0 / _shape1 in their order: the flat order restricted to one world is its analytic slots, its
+ *     convex slots (= ascending slot index), then its live rows.
+ *
+ * world_mask ([env_count] uint8, nullable): rows of unselected worlds are neither computed nor written.  Every selected world's whole
+ * output row is written on every call, zeros included.
+ *
+ * The tables are validated on the host copies (slot_sensing_host / slot_counterpart_host, [ns + ng] each; slot_counterpart_host may
+ * be NULL when C == 0).  NT_ERR_INVALID_ARG before any launch: NULL arguments, S <= 0, C < 0, no column at all (include_total + C
+ * == 0), an entry outside its range, dt <= 0 or not finite, a flat.impulse without row_start / shape0 / shape1.  The mapping has no
+ * LDS bound (the contacts of a world pass through a fixed staging buffer in chunks), so no argument is answered
+ * NT_ERR_UNSUPPORTED. */
+typedef struct {
+    int32_t sensing_count;                /* S >= 1 */
+    int32_t counterpart_count;            /* C >= 0 */
+    int32_t include_total;                /* 0 / 1 */
+    int32_t row_capacity;                 /* capacity of nt_contacts.flat (0: its rows are not read) */
+    const int32_t* slot_sensing;          /* [ns + ng] device */
+    const int32_t* slot_counterpart;      /* [ns + ng] device (NULL allowed when C == 0) */
+    const int32_t* slot_sensing_host;     /* the same tables on the host: what the entry point validates */
+    const int32_t* slot_counterpart_host;
+    const uint8_t* world_mask;            /* [env_count] device or NULL */
+    float* net_force;                     /* [env_count][S][include_total + C][3] device, out */
+} nt_contact_sensor_args;
+
+/* contact_impulse: [6][np*cpp][ES], what nt_xpbd_step wrote through the contact_impulse member of its report; NULL allowed only when
+ * the model has no slots */
+nt_status nt_contact_sensor(const nt_model* m, const nt_contacts* c, const float* contact_impulse, float dt,
+                            const nt_contact_sensor_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

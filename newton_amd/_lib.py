@@ -264,6 +264,13 @@ class nt_contact_group(C.Structure):
                 ("row_capacity", C.c_int32), ("slot_flat", C.c_void_p), ("row_flat", C.c_void_p), ("r", C.POINTER(nt_contact_report))]
 
 
+class nt_contact_sensor_args(C.Structure):
+    """include/newton_hip_contacts.h: net contact force per world on sets of shape slots (newton_amd.sensors.SensorContact)."""
+    _fields_ = [("sensing_count", C.c_int32), ("counterpart_count", C.c_int32), ("include_total", C.c_int32), ("row_capacity", C.c_int32),
+                ("slot_sensing", C.c_void_p), ("slot_counterpart", C.c_void_p), ("slot_sensing_host", C.c_void_p),
+                ("slot_counterpart_host", C.c_void_p), ("world_mask", C.c_void_p), ("net_force", C.c_void_p)]
+
+
 class nt_hydro_args(C.Structure):
     _fields_ = [("pairs", C.c_void_p), ("pair_count", C.c_int32), ("shape_transform", C.c_void_p), ("shape_data", C.c_void_p),
                 ("shape_gap", C.c_void_p), ("shape_kh", C.c_void_p), ("shape_sdf_index", C.c_void_p), ("sdf_table", C.c_void_p),
@@ -456,6 +463,7 @@ SYMBOLS = {
                                                     C.POINTER(nt_contact_report), _P]),
     "nt_contacts_order_save_groups": (C.c_int32, [C.c_int32, C.POINTER(nt_contact_group), C.POINTER(nt_sorted_contacts),
                                                   C.POINTER(nt_contact_report), _P]),
+    "nt_contact_sensor": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_contacts), _P, C.c_float, C.POINTER(nt_contact_sensor_args), _P]),
     # include/newton_hip_kinematics.h
     "nt_eval_ik": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_state), _P, _P, _P, _P]),
     "nt_eval_ik_tile": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_state), _P, _P, _P, C.c_int32, _P]),

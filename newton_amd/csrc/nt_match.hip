@@ -815,3 +815,161 @@ nt_status nt_contacts_order_save_groups(int32_t group_count, const nt_contact_gr
 }
 
 }  // extern "C"
+
+// ---- nt_contact_sensor (newton_amd.sensors.SensorContact; contract: include/newton_hip_contacts.h) -----------------------------------
+// Net contact force per world on S sets of shapes, split by C counterparts, straight from the slot-major contacts and the rows.
+// A workgroup of CS_THREADS lanes serves wpb worlds (CS_THREADS / wpb lanes each; wpb shrinks from CS_MAX_WPB while a world has more
+// output cells than lanes).  The entries of a world -- its slots in ascending index, then its rows -- pass through a fixed staging
+// buffer of CS_ITEMS records in rounds of CS_ITEMS / wpb entries per world: one (entry, world) per lane with the world the fastest index
+// (the env-major [slot][ES] arrays are read in runs of wpb consecutive floats), resolved to (sensing object and counterpart of either
+// shape, f[3]) once.  After the barrier one lane per output cell walks the round's records of its world in entry order and adds in
+// registers: the lanes of a world read the same record (LDS broadcast), different worlds neighbouring words (the records are SoA with
+// the world innermost: no bank conflict).  A cell is owned by one lane from the first entry to the last, so the sum is the contract's
+// sequential one whatever wpb is; worlds with more cells than lanes take further passes over the same entries.
+namespace {
+
+constexpr int CS_THREADS = 256;  // lanes of a workgroup
+constexpr int CS_MAX_WPB = 16;   // worlds per workgroup, at most (a power of two)
+constexpr int CS_ITEMS = 512;    // staged records per round, over the workgroup's worlds: 7 words each, 14 KB of LDS
+
+// shape slot of a world (env-local slots, then the global shapes) that carries Newton shape id `id`, -1: none of this world's
+__device__ inline int cs_slot_of(const nt_model& m, int e, int id) {
+    const int l = id - m.shape_local0 - e * m.ns;
+    if (id >= 0 && l >= 0 && l < m.ns) return l;
+    for (int k = 0; k < m.ng; ++k)
+        if (m.gshape_id[k] == id) return m.ns + k;
+    return -1;
+}
+__device__ inline int cs_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+__global__ void __launch_bounds__(CS_THREADS) contact_sensor_kernel(nt_model m, nt_contacts c, const float* __restrict__ impulse, float inv_dt,
+                                                                    nt_contact_sensor_args a, int wpb) {
+    __shared__ int32_t cs_side[2][CS_ITEMS];   // sensing object of shape0 / shape1 (-1: none; both -1: nothing to add)
+    __shared__ int32_t cs_other[2][CS_ITEMS];  // counterpart of shape0 / shape1
+    __shared__ float cs_f[3][CS_ITEMS];
+    const int tid = threadIdx.x, E = m.env_count, nslot = m.np * m.cpp;
+    const size_t ES = (size_t)m.env_stride;
+    const int rl = CS_THREADS / wpb, chunk = CS_ITEMS / wpb;
+    const int S = a.sensing_count, cols = a.include_total + a.counterpart_count, cells = S * cols;
+    const nt_flat_rows& fr = c.flat;
+    const bool rows = a.row_capacity > 0 && fr.impulse != nullptr;
+    const int nf = rows ? cs_clamp(fr.row_start[E], a.row_capacity) : 0;
+    const int groups = (E + wpb - 1) / wpb;
+    const int wl = tid / rl, ln = tid - wl * rl;
+    for (int g = blockIdx.x; g < groups; g += gridDim.x) {
+        // the longest entry list of the group's selected worlds: the trip count of the rounds, uniform over the workgroup
+        int longest = nslot;
+        if (rows)
+            for (int u = 0; u < wpb; ++u) {
+                const int eu = g * wpb + u;
+                if (eu >= E || (a.world_mask && !a.world_mask[eu])) continue;
+                const int n = nslot + cs_clamp(fr.row_start[eu + 1], nf) - cs_clamp(fr.row_start[eu], nf);
+                longest = n > longest ? n : longest;
+            }
+        const int e = g * wpb + wl;
+        const bool live = e < E && !(a.world_mask && !a.world_mask[e]);
+        int n_e = nslot;
+        if (live && rows) {
+            const int n = nslot + cs_clamp(fr.row_start[e + 1], nf) - cs_clamp(fr.row_start[e], nf);
+            n_e = n > n_e ? n : n_e;
+        }
+        for (int cell0 = 0; cell0 < cells; cell0 += rl) {
+            const int cell = cell0 + ln;
+            const bool active = live && cell < cells;
+            const int s = cell / cols, col = cell - s * cols, cp = col - a.include_total;  // cp < 0: the total column
+            float ax = 0.0f, ay = 0.0f, az = 0.0f;
+            for (int base = 0; base < longest; base += chunk) {
+                __syncthreads();  // the previous round's records are no longer read
+                for (int item = tid; item < CS_ITEMS; item += CS_THREADS) {
+                    const int j = item / wpb, u = item - j * wpb, eu = g * wpb + u, n = base + j;
+                    int k0 = -1, k1 = -1;
+                    if (eu < E && !(a.world_mask && !a.world_mask[eu])) {
+                        int s0 = -1, s1 = -1;
+                        const float* f = nullptr;
+                        size_t stride = 1;
+                        if (n < nslot) {
+                            const size_t gi = (size_t)n * ES + eu;
+                            s0 = c.shape0[gi];
+                            if (s0 >= 0) {
+                                s1 = c.shape1[gi];
+                                f = impulse + gi;
+                                stride = (size_t)nslot * ES;
+                            }
+                        } else if (rows) {
+                            const int r0 = cs_clamp(fr.row_start[eu], nf), r1 = cs_clamp(fr.row_start[eu + 1], nf), r = r0 + (n - nslot);
+                            if (r < r1) {
+                                s0 = fr.shape0[r];
+                                s1 = fr.shape1[r];
+                                if (s0 != s1) f = fr.impulse + 6 * (size_t)r;
+                            }
+                        }
+                        if (f) {
+                            const int a0 = cs_slot_of(m, eu, s0), a1 = cs_slot_of(m, eu, s1);
+                            k0 = a0 >= 0 ? a.slot_sensing[a0] : -1;
+                            k1 = a1 >= 0 ? a.slot_sensing[a1] : -1;
+                            if (k0 >= 0 || k1 >= 0) {
+                                const bool cps = a.counterpart_count > 0;
+                                cs_other[0][item] = cps && a0 >= 0 ? a.slot_counterpart[a0] : -1;
+                                cs_other[1][item] = cps && a1 >= 0 ? a.slot_counterpart[a1] : -1;
+                                cs_f[0][item] = f[0] * inv_dt;
+                                cs_f[1][item] = f[stride] * inv_dt;
+                                cs_f[2][item] = f[2 * stride] * inv_dt;
+                            }
+                        }
+                    }
+                    cs_side[0][item] = k0;
+                    cs_side[1][item] = k1;
+                }
+                __syncthreads();
+                if (active) {
+                    const int left = n_e - base, jn = left < chunk ? left : chunk;
+                    for (int j = 0; j < jn; ++j) {  // entry order
+                        const int item = j * wpb + wl;
+                        const int k0 = cs_side[0][item], k1 = cs_side[1][item];
+                        if (k0 == s && (cp < 0 || cs_other[1][item] == cp)) {  // on the sensing object as shape0: +f
+                            ax = ax + cs_f[0][item];
+                            ay = ay + cs_f[1][item];
+                            az = az + cs_f[2][item];
+                        }
+                        if (k1 == s && (cp < 0 || cs_other[0][item] == cp)) {  // as shape1: -f
+                            ax = ax - cs_f[0][item];
+                            ay = ay - cs_f[1][item];
+                            az = az - cs_f[2][item];
+                        }
+                    }
+                }
+            }
+            if (active) {
+                float* out = a.net_force + 3 * ((size_t)e * cells + cell);
+                out[0] = ax; out[1] = ay; out[2] = az;
+            }
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" nt_status nt_contact_sensor(const nt_model* m, const nt_contacts* c, const float* contact_impulse, float dt,
+                                       const nt_contact_sensor_args* a, void* stream) {
+    if (!m || !c || !a || !a->slot_sensing || !a->slot_sensing_host || !a->net_force || a->sensing_count <= 0 || a->counterpart_count < 0 ||
+        (a->include_total != 0 && a->include_total != 1) || a->include_total + a->counterpart_count <= 0 || a->row_capacity < 0 ||
+        !(dt > 0.0f) || !(dt <= 3.0e38f) || m->env_count <= 0 || m->env_stride < m->env_count || m->ns < 0 || m->ng < 0 || m->np < 0 ||
+        m->cpp < 0 || m->ns + m->ng <= 0 || (m->ng > 0 && !m->gshape_id))
+        return NT_ERR_INVALID_ARG;
+    if (a->counterpart_count > 0 && (!a->slot_counterpart || !a->slot_counterpart_host)) return NT_ERR_INVALID_ARG;
+    if ((long long)m->np * m->cpp > 0 && (!c->shape0 || !c->shape1 || !contact_impulse)) return NT_ERR_INVALID_ARG;
+    if (a->row_capacity > 0 && c->flat.impulse && (!c->flat.row_start || !c->flat.shape0 || !c->flat.shape1)) return NT_ERR_INVALID_ARG;
+    for (int k = 0; k < m->ns + m->ng; ++k) {
+        if (a->slot_sensing_host[k] < -1 || a->slot_sensing_host[k] >= a->sensing_count) return NT_ERR_INVALID_ARG;
+        if (a->counterpart_count > 0 && (a->slot_counterpart_host[k] < -1 || a->slot_counterpart_host[k] >= a->counterpart_count))
+            return NT_ERR_INVALID_ARG;
+    }
+    const long long cells = (long long)a->sensing_count * (a->include_total + a->counterpart_count);
+    if (cells > 0x7fffffffLL / 4 / m->env_count) return NT_ERR_INVALID_ARG;  // (the cell index of a world stays an int)
+    // worlds per workgroup: as many as still leave every output cell of a world a lane of its own
+    int wpb = CS_MAX_WPB;
+    while (wpb > 1 && wpb * cells > CS_THREADS) wpb /= 2;
+    hipLaunchKernelGGL(contact_sensor_kernel, dim3(grid_for(((size_t)m->env_count + wpb - 1) / wpb, 1)), dim3(CS_THREADS), 0,
+                       (hipStream_t)stream, *m, *c, contact_impulse, 1.0f / dt, *a, wpb);
+    return hipGetLastError() == hipSuccess ? NT_OK : NT_ERR_LAUNCH;
+}

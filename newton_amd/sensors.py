@@ -1,4 +1,5 @@
-"""Ray-cast sensors: ``SensorRaycast`` casts R rays per world against the shapes of that world -- a height scan under a robot's base,
+"""Sensors.  ``SensorContact`` (further down): the net contact force per world on chosen bodies / shapes, split by counterpart.
+Ray-cast sensors: ``SensorRaycast`` casts R rays per world against the shapes of that world -- a height scan under a robot's base,
 a lidar sweep over the other bodies.  The capability of the reference's ``newton.sensors.SensorRaycast``; that one is a single
 camera, this one is ONE SENSOR PER WORLD of the replicated model, because that is what the batched layout serves: the same R rays
 (or R rays of its own) in every world, attached to a body of that world or fixed in the world frame.
@@ -435,3 +436,157 @@ class SensorRaycast:
             self.normal[sel] = normal[sel]
         if self.shape is not None:
             self.shape[sel] = shape[sel]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# SensorContact: net contact force per world on chosen bodies / shapes, split by counterpart (nt_contact_sensor, contract in
+# include/newton_hip_contacts.h)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def contact_sensor_numpy(model, count, shape0, shape1, force, slot_sensing, slot_counterpart, sensing_count, counterpart_count,
+                         include_total=True, world_mask=None, dtype=np.float64):
+    """The contract of nt_contact_sensor over Newton's flat arrays: net_force [E, S, include_total + C, 3] in ``dtype`` (float64: the
+    reference the kernel is tested against; float32: the kernel's own sequential sum when the flat order is the raw export order).
+    ``count`` / ``shape0`` / ``shape1`` / ``force``: rigid_contact_count, rigid_contact_shape0 / _shape1 and Contacts.force (its linear
+    part is read); every world's entries are added in their flat order, +f on the sensing object of shape0, then -f on that of shape1.
+    The world of an entry is that of its env-local shape; entries with shape0 < 0, with shape0 == shape1 or between shapes of no one
+    world are skipped.  Rows of worlds outside ``world_mask`` stay zero."""
+    t = model.env
+    E, ns, lo = t.env_count, t.ns, t.shape_local0
+    S, Cn, tot = int(sensing_count), int(counterpart_count), int(bool(include_total))
+    sens = np.asarray(slot_sensing, dtype=np.int64).reshape(-1)
+    cpart = np.full(ns + t.ng, -1, np.int64) if Cn == 0 else np.asarray(slot_counterpart, dtype=np.int64).reshape(-1)
+    gslot = {int(g): ns + k for k, g in enumerate(np.asarray(t.gshape_id).reshape(-1)[:t.ng])}
+    n = int(np.asarray(_host_array(count)).reshape(-1)[0])
+    s0 = np.asarray(_host_array(shape0)).reshape(-1)
+    s1 = np.asarray(_host_array(shape1)).reshape(-1)
+    f = np.asarray(_host_array(force)).reshape(len(s0), -1)[:, :3].astype(dtype)
+    n = min(n, len(s0))
+    mask = None if world_mask is None else np.asarray(_host_array(world_mask)).astype(bool).reshape(E)
+    out = np.zeros((E, S, tot + Cn, 3), dtype=dtype)
+
+    def locate(i):  # (world or -1 for a global shape, slot or -1)
+        if lo <= i < lo + E * ns:
+            return (i - lo) // ns, (i - lo) % ns
+        return -1, gslot.get(i, -1)
+
+    for i in range(n):
+        a, b = int(s0[i]), int(s1[i])
+        if a < 0 or a == b:
+            continue
+        (wa, sa), (wb, sb) = locate(a), locate(b)
+        w = wa if wa >= 0 else wb
+        if w < 0 or (wa >= 0 and wb >= 0 and wa != wb) or (mask is not None and not mask[w]):
+            continue
+        for mine, other, sign in ((sa, sb, 1), (sb, sa, -1)):
+            k = sens[mine] if mine >= 0 else -1
+            if k < 0:
+                continue
+            c = cpart[other] if other >= 0 else -1
+            if tot:
+                out[w, k, 0] = out[w, k, 0] + f[i] if sign > 0 else out[w, k, 0] - f[i]
+            if c >= 0:
+                out[w, k, tot + c] = out[w, k, tot + c] + f[i] if sign > 0 else out[w, k, tot + c] - f[i]
+    return out
+
+
+class SensorContact:
+    """Net contact force on chosen bodies / shapes of every world, split by counterpart (the capability of the reference's
+    ``newton.sensors.SensorContact``): feet against the ground give contact flags, air time and reward terms.
+
+    Indices are env-local.  ``sensing_bodies`` / ``counterpart_bodies``: bodies 0 .. nb-1, a body meaning every shape it carries;
+    ``sensing_shapes`` / ``counterpart_shapes``: shape slots 0 .. ns+ng-1, the global shapes addressed as ns + k (the ground plane).
+    The sensing objects are the bodies in the given order, then the shapes (``sensing_labels``, a list of ("body", i) / ("shape", slot));
+    the counterparts likewise (``counterpart_labels``).  A shape slot belongs to at most one sensing object and at most one counterpart.
+
+    ``eval(contacts)`` fills ``net_force`` [world, S, include_total + C, 3], the force ON the sensing object: column 0 the total over
+    all its contacts (with ``include_total``), column include_total + c the part exchanged with counterpart c; ``shape`` is
+    (S, include_total + C).  GPU model: one launch of contact_sensor_kernel on the model's stream straight from the contacts a
+    ``SolverXPBD.step`` reported its impulses into (``model.request_contact_attributes("force")`` before the Contacts are created;
+    ``update_contacts`` is neither needed nor called), float32, every cell a sequential sum over the world's slots, then its SDF-leg
+    rows; recordable by ``newton_amd.graph.capture``.  Host model, or any object with numpy ``rigid_contact_count`` /
+    ``rigid_contact_shape0`` / ``rigid_contact_shape1`` / ``force``: the same contract in float64 (``contact_sensor_numpy``)."""
+
+    def __init__(self, model, sensing_bodies=(), sensing_shapes=(), counterpart_bodies=(), counterpart_shapes=(), include_total=True):
+        if getattr(model, "is_heterogeneous", False):
+            raise NotImplementedError("SensorContact: heterogeneous models are unsupported (one sensor is S sensing objects in every world of a replicated model)")
+        t = model.env
+        nslot = t.ns + t.ng
+        self.model, self.include_total = model, bool(include_total)
+        shape_body = np.asarray(t.shape_body).reshape(-1)[:nslot]
+
+        def table(bodies, shapes, what):
+            tab, labels = np.full(nslot, -1, np.int32), []
+            for kind, idx in [("body", b) for b in bodies] + [("shape", s) for s in shapes]:
+                idx, hi = int(idx), (t.nb if kind == "body" else nslot)
+                if not 0 <= idx < hi:
+                    raise ValueError(f"SensorContact: {what} {kind} {idx} is out of range (env-local 0 .. {hi - 1})")
+                slots = np.flatnonzero(shape_body == idx) if kind == "body" else np.array([idx])
+                for slot in slots:
+                    if tab[slot] >= 0:
+                        raise ValueError(f"SensorContact: shape slot {int(slot)} is claimed by two {what} objects, "
+                                         f"{labels[tab[slot]]} and {(kind, idx)}")
+                    tab[slot] = len(labels)
+                labels.append((kind, idx))
+            return tab, labels
+
+        self.slot_sensing, self.sensing_labels = table(sensing_bodies, sensing_shapes, "sensing")
+        self.slot_counterpart, self.counterpart_labels = table(counterpart_bodies, counterpart_shapes, "counterpart")
+        if not self.sensing_labels:
+            raise ValueError("SensorContact: no sensing object (give sensing_bodies and / or sensing_shapes)")
+        S, cols = len(self.sensing_labels), int(self.include_total) + len(self.counterpart_labels)
+        if cols == 0:
+            raise ValueError("SensorContact: no output column (include_total is off and there is no counterpart)")
+        self.shape = (S, cols)
+        self._gpu = bool(getattr(model, "is_gpu", False))
+        if self._gpu:
+            import torch  # noqa: PLC0415
+
+            from . import _lib  # noqa: PLC0415
+
+            dev = model.device_model().device
+            self.net_force = torch.zeros((t.env_count, S, cols, 3), dtype=torch.float32, device=dev)
+            self._world_mask = torch.ones(t.env_count, dtype=torch.uint8, device=dev)
+            self._tables = (torch.from_numpy(self.slot_sensing).to(dev), torch.from_numpy(self.slot_counterpart).to(dev))
+            a = _lib.nt_contact_sensor_args()
+            a.sensing_count, a.counterpart_count, a.include_total = S, len(self.counterpart_labels), int(self.include_total)
+            a.slot_sensing, a.slot_counterpart = self._tables[0].data_ptr(), self._tables[1].data_ptr()
+            a.slot_sensing_host, a.slot_counterpart_host = self.slot_sensing.ctypes.data, self.slot_counterpart.ctypes.data
+            a.net_force = self.net_force.data_ptr()
+            self._args = a
+        else:
+            self.net_force = np.zeros((t.env_count, S, cols, 3))
+
+    def eval(self, contacts, world_mask=None):
+        """Sum the contact forces of ``contacts``.  ``world_mask`` ([world] bool): the rows of unselected worlds are neither computed
+        nor written.  GPU model: one kernel launch on the model's stream (the mask is copied into a resident buffer first)."""
+        t = self.model.env
+        if world_mask is not None and int(np.prod(np.shape(world_mask))) != t.env_count:
+            raise ValueError(f"world_mask must have {t.env_count} entries")
+        S, Cn = len(self.sensing_labels), len(self.counterpart_labels)
+        if self._gpu:
+            from . import _lib  # noqa: PLC0415
+
+            if getattr(contacts, "force", None) is None or getattr(contacts, "_impulse", None) is None:
+                raise ValueError("SensorContact.eval: contacts.force is not allocated. Call model.request_contact_attributes('force') "
+                                 "before creating the Contacts object.")
+            dt = getattr(contacts, "_impulse_dt", None)
+            if dt is None:
+                raise ValueError("SensorContact.eval: no contact impulses on these contacts. Call SolverXPBD.step() with them first.")
+            dm = self.model.device_model()
+            if world_mask is not None:
+                import torch  # noqa: PLC0415
+
+                wm = world_mask if hasattr(world_mask, "data_ptr") else torch.from_numpy(np.asarray(world_mask).astype(np.uint8))
+                self._world_mask.copy_(wm.reshape(-1).to(torch.uint8))
+            a = self._args
+            a.world_mask = None if world_mask is None else self._world_mask.data_ptr()
+            flat = getattr(contacts, "_flat", None)
+            a.row_capacity = int(flat.capacity) if flat is not None and flat.impulse is not None else 0
+            d = contacts._desc()
+            _lib.check(dm.lib.nt_contact_sensor(C.byref(dm.desc), C.byref(d), contacts._impulse.data_ptr(), float(dt), C.byref(a),
+                                                dm.stream()), "nt_contact_sensor")
+            return
+        out = contact_sensor_numpy(self.model, contacts.rigid_contact_count, contacts.rigid_contact_shape0, contacts.rigid_contact_shape1,
+                                   contacts.force, self.slot_sensing, self.slot_counterpart, S, Cn, self.include_total, world_mask)
+        sel = slice(None) if world_mask is None else np.asarray(_host_array(world_mask)).astype(bool).reshape(-1)
+        self.net_force[sel] = out[sel]

@@ -68,6 +68,8 @@ class SolverXPBD(SolverBase):
             reporting = True
         self._contact_impulse_capacity = contacts.rigid_contact_max if contacts is not None else 0
         self._last_dt = float(dt)
+        if self._contact_impulse is not None:
+            contacts._impulse_dt = self._last_dt  # (sensors.SensorContact reads the impulses straight from `contacts`)
         if state_out._parent_f is not None and self.model.env.nj > 0:
             if self._joint_impulse is None:
                 import torch  # noqa: PLC0415
