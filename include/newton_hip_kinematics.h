@@ -158,6 +158,61 @@ nt_status nt_ik_solve(const nt_model* m, const nt_ik_problem* p, const float* jo
 nt_status nt_ik_solve_tile(const nt_model* m, const nt_ik_problem* p, const float* joint_q_in, float* joint_q_out, float* lambda, float* cost,
                            int32_t iterations, float step_size, int32_t envs_per_block, void* stream);
 
+/* Frame sensors (the capability of the reference's newton.sensors.SensorFrameTransform and newton.sensors.SensorIMU;
+ * newton_amd.sensors.SensorFrameTransform / SensorIMU):
+ *   nt_frame_sensor       <- SensorFrameTransform.update(state) / SensorIMU.update(state)               newton/_src/sensors/
+ * A frame is owned by the caller, not by the model: an env-local body (or -1: fixed in the world) and a transform (p_l, q_l xyzw) in
+ * that body.  The table of M frames is the same in every world; each of the N output rows of a world names the frame it measures
+ * (out_frame) and the frame it is expressed in (out_ref, -1: the world).  One launch of frame_sensor_kernel straight from the env-major
+ * state: no staging, no LDS, no scratch state.
+ *
+ * For a frame on body b with body pose (p, q) = s->body_q[b], COM c = rows 0..2 of nt_model.body_param (body frame) and
+ * (v_com, w) = s->body_qd[b] (the linear part is the COM velocity, newton_hip.h):
+ *   x = p + rot(q, p_l),  q_f = q * q_l,  r = rot(q, p_l - c),  v = v_com + w x r;
+ * for body -1:  x = p_l,  q_f = q_l,  v = w = r = 0.  g is this world's row of nt_model.gravity ([3][ES]; a run-time change of the
+ * model's gravity is seen by the next call).  Outputs, per (world, row); every pointer may be NULL, not all of them:
+ *   transform   [env_count][N][7]  (rot_inv(q_ref, x - x_ref), q_ref^-1 * q_f) = X_ref^-1 X_frame; out_ref = -1: (x, q_f)
+ *   velocity    [env_count][N][6]  (rot_inv(q_f, v), rot_inv(q_f, w)): the velocity of the frame origin and the angular velocity in
+ *                                  the frame's own axes.  Absolute: out_ref plays no part
+ *   gravity_dir [env_count][N][3]  rot_inv(q_f, g / |g|), zeros when the world's gravity is zero
+ *   accel       [env_count][N][3]  the specific force an accelerometer at the frame origin reads, in the frame's axes:
+ *                                  rot_inv(q_f, (v_com - v_com_prev) / dt + ((w - w_prev) / dt) x r + w x (w x r) - g).
+ *                                  q, r and w are those of `s`; v_com_prev and w_prev = prev->body_qd[b] are all that is read from
+ *                                  `prev`, which comes as a whole nt_state so that the caller hands over the previous state's
+ *                                  descriptor unchanged.  dt is the time between the two states; the reading is the MEAN acceleration
+ *                                  over that interval (the model carries no body_qdd).  prev == s is allowed: the centripetal term
+ *                                  minus gravity.  A frame fixed in the world reads rot_inv(q_l, -g).
+ * Plain float32 IEEE arithmetic (no contraction, correctly rounded division and square root) in one fixed expression per output
+ * element: replicated worlds in equal states give equal bits.  Every selected world's whole row of every non-NULL output is written
+ * by every call; world_mask ([env_count] bytes or NULL): the rows of unselected worlds are neither computed nor written.
+ *
+ * The tables are read on the device through frame_body / frame_xform / out_frame / out_ref; the *_host pointers are host copies of the
+ * same arrays, and they are what this call validates (it does not synchronise, so it cannot look at device memory).  Same conventions
+ * as above: no allocation, no synchronisation, no atomics, the launch shape depends on env_count and N alone -- recordable by
+ * nt_graph_capture_begin / _end.  Errors, all NT_ERR_INVALID_ARG and all before any launch: a null m / s / a, a model without bodies,
+ * a null table (device or host copy) or a null state array an output needs (body_q; body_qd for velocity and accel); M <= 0 or N <= 0;
+ * every output pointer null; a frame_body outside -1 .. nb-1; an out_frame outside 0 .. M-1 or an out_ref outside -1 .. M-1; a
+ * frame_xform entry that is not finite or a quaternion whose norm differs from 1 by more than 1e-4; accel with a null prev (or a prev
+ * without body_qd), with dt <= 0 or with a dt that is not finite.  Nothing is answered NT_ERR_UNSUPPORTED. */
+typedef struct nt_frame_sensor_args {
+    int32_t frame_count;            /* M >= 1 frames in the table */
+    const int32_t* frame_body;      /* [M] device: env-local body 0..nb-1, or -1 = fixed in the world */
+    const float*   frame_xform;     /* [M][7] device: (p, q xyzw) of the frame in its body (in the world for body -1) */
+    int32_t out_count;              /* N >= 1 output rows per world */
+    const int32_t* out_frame;       /* [N] device: table index measured */
+    const int32_t* out_ref;         /* [N] device: table index it is expressed in, -1 = the world */
+    const int32_t* frame_body_host; const float* frame_xform_host;   /* host copies: what the entry point validates */
+    const int32_t* out_frame_host;  const int32_t* out_ref_host;
+    const uint8_t* world_mask;      /* [env_count] device or NULL */
+    float* transform;               /* [env_count][N][7] or NULL: X_ref^-1 X_frame */
+    float* velocity;                /* [env_count][N][6] or NULL: (linear velocity of the frame origin, angular velocity), in the frame's own axes */
+    float* gravity_dir;             /* [env_count][N][3] or NULL: unit gravity direction in the frame's axes (0 when the world's gravity is 0) */
+    float* accel;                   /* [env_count][N][3] or NULL: specific force in the frame's axes; needs `prev` */
+} nt_frame_sensor_args;
+
+nt_status nt_frame_sensor(const nt_model* m, const nt_state* s, const nt_state* prev /* NULL unless accel */, float dt,
+                          const nt_frame_sensor_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -271,6 +271,15 @@ class nt_contact_sensor_args(C.Structure):
                 ("slot_counterpart_host", C.c_void_p), ("world_mask", C.c_void_p), ("net_force", C.c_void_p)]
 
 
+class nt_frame_sensor_args(C.Structure):
+    """include/newton_hip_kinematics.h: pose / velocity / gravity direction / specific force of caller-owned frames
+    (newton_amd.sensors.SensorFrameTransform, SensorIMU)."""
+    _fields_ = [("frame_count", C.c_int32), ("frame_body", C.c_void_p), ("frame_xform", C.c_void_p), ("out_count", C.c_int32),
+                ("out_frame", C.c_void_p), ("out_ref", C.c_void_p), ("frame_body_host", C.c_void_p), ("frame_xform_host", C.c_void_p),
+                ("out_frame_host", C.c_void_p), ("out_ref_host", C.c_void_p), ("world_mask", C.c_void_p), ("transform", C.c_void_p),
+                ("velocity", C.c_void_p), ("gravity_dir", C.c_void_p), ("accel", C.c_void_p)]
+
+
 class nt_hydro_args(C.Structure):
     _fields_ = [("pairs", C.c_void_p), ("pair_count", C.c_int32), ("shape_transform", C.c_void_p), ("shape_data", C.c_void_p),
                 ("shape_gap", C.c_void_p), ("shape_kh", C.c_void_p), ("shape_sdf_index", C.c_void_p), ("sdf_table", C.c_void_p),
@@ -473,6 +482,7 @@ SYMBOLS = {
     "nt_eval_mass_matrix_tile": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_state), _P, _P, _P, C.c_int32, _P]),
     "nt_ik_solve": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_ik_problem), _P, _P, _P, _P, C.c_int32, C.c_float, _P]),
     "nt_ik_solve_tile": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_ik_problem), _P, _P, _P, _P, C.c_int32, C.c_float, C.c_int32, _P]),
+    "nt_frame_sensor": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_state), C.POINTER(nt_state), C.c_float, C.POINTER(nt_frame_sensor_args), _P]),
     "nt_hydro_collide": (C.c_int32, [C.POINTER(nt_hydro_args), _P]),
     "nt_hydro_pairs": (C.c_int32, [C.POINTER(nt_hydro_args), _P]),
     "nt_sdf_candidate_pairs": (C.c_int32, [C.POINTER(nt_sdf_scene), _P, _P, _P, _P, _P, _P]),

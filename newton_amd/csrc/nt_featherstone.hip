@@ -1,7 +1,7 @@
 // nt_featherstone.hip -- SolverFeatherstone (step / fused rollout), eval_fk and eval_ik: launch code + C ABI.  The solver's kernels are
 // nt_featherstone_kernels.hpp, their phases nt_featherstone.hpp (namespace ieee); this unit exists so that they are compiled with the
-// default scheduler (see nt_step_preamble.hpp).  eval_ik, eval_jacobian and eval_mass_matrix (kernels and entry points,
-// include/newton_hip_kinematics.h) live here whole: the headers the stepping unit shares stay as they are.
+// default scheduler (see nt_step_preamble.hpp).  eval_ik, eval_jacobian, eval_mass_matrix, ik_solve and frame_sensor (kernels and entry
+// points, include/newton_hip_kinematics.h) live here whole: the headers the stepping unit shares stay as they are.
 #include "nt_step_preamble.hpp"
 #ifndef NT_EMULATED_GRID
 #include "../../include/newton_hip_kinematics.h"
@@ -168,6 +168,108 @@ __global__ void __launch_bounds__(256) eval_ik_kernel(KArgs a, float* joint_q, f
         const int d0 = c.T.joint_qd_start[j0], d1 = j1 < m.nj ? c.T.joint_qd_start[j1] : m.nd;
         unstage_rows(c, oq + q0, joint_q + (size_t)q0 * c.ES, q1 - q0);
         unstage_rows(c, oqd + d0, joint_qd + (size_t)d0 * c.ES, d1 - d0);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// nt_frame_sensor (newton_amd.sensors.SensorFrameTransform / SensorIMU; contract: include/newton_hip_kinematics.h): pose, velocity,
+// gravity direction and specific force of caller-owned frames, straight from the env-major state.  One lane per (output row, world)
+// with the world the fastest index: a workgroup is ONE wave that takes one row for 64 consecutive worlds, so every body_q / body_qd /
+// body_param / gravity read is a run of 64 consecutive floats, and the row's table entries (frames, bodies, local transforms) are the
+// same in every lane -- they come in through scalar loads.  The (row, 64 worlds) items are handed out grid-stride.  No LDS, no barrier,
+// no atomics; the outputs are the public [world][row][comp] arrays, each lane writing the 3 / 6 / 7 consecutive floats of its row.
+// ------------------------------------------------------------------------------------------------
+constexpr int FR_THREADS = 64;     // lanes of a workgroup: one wave, 64 consecutive worlds of one output row
+constexpr int FR_MAX_GRID = 8192;  // workgroups at most (32 waves for each of 256 CUs); what is left is taken grid-stride
+
+struct FrFrame {
+    vec3 x, r, vc, v, w;  // origin, origin - COM (world axes), COM velocity, velocity of the origin, angular velocity
+    quat q;
+    int body;
+};
+
+NT_DI vec3 fr_load3(const float* base, int c0, int n, int slot, size_t ES, int e) {
+    return vec3(base[((size_t)(c0 + 0) * n + slot) * ES + e], base[((size_t)(c0 + 1) * n + slot) * ES + e],
+                base[((size_t)(c0 + 2) * n + slot) * ES + e]);
+}
+NT_DI int fr_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// pose of table frame f in world e; with `vel` its r, v and w too
+NT_DI FrFrame fr_frame(const nt_model& m, const float* body_q, const float* body_qd, const nt_frame_sensor_args& a, int f, int e, bool vel) {
+    const size_t ES = (size_t)m.env_stride;
+    const float* X = a.frame_xform + 7 * (size_t)f;
+    const vec3 pl(X[0], X[1], X[2]);
+    const quat ql(X[3], X[4], X[5], X[6]);
+    FrFrame F;
+    F.body = fr_clamp(a.frame_body[f], -1, m.nb - 1);  // (the entry point refuses other values in the host copy)
+    if (F.body < 0) {
+        F.x = pl;
+        F.q = ql;
+        return F;
+    }
+    const vec3 p = fr_load3(body_q, 0, m.nb, F.body, ES, e);
+    const quat q(body_q[((size_t)3 * m.nb + F.body) * ES + e], body_q[((size_t)4 * m.nb + F.body) * ES + e],
+                 body_q[((size_t)5 * m.nb + F.body) * ES + e], body_q[((size_t)6 * m.nb + F.body) * ES + e]);
+    F.x = p + quat_rotate(q, pl);
+    F.q = q * ql;
+    if (vel) {
+        F.r = quat_rotate(q, pl - fr_load3(m.body_param, BP_COM, m.nb, F.body, ES, e));
+        F.w = fr_load3(body_qd, 3, m.nb, F.body, ES, e);
+        F.vc = fr_load3(body_qd, 0, m.nb, F.body, ES, e);
+        F.v = F.vc + cross(F.w, F.r);
+    }
+    return F;
+}
+
+__global__ void __launch_bounds__(FR_THREADS) frame_sensor_kernel(nt_model m, const float* body_q, const float* body_qd, const float* prev_qd,
+                                                                  float dt, nt_frame_sensor_args a) {
+    const int E = m.env_count, N = a.out_count, M = a.frame_count;
+    const size_t ES = (size_t)m.env_stride;
+    const int chunks = (E + FR_THREADS - 1) / FR_THREADS, items = chunks * N;
+    const bool vel = a.velocity || a.accel;
+    for (int item = blockIdx.x; item < items; item += gridDim.x) {
+        const int n = item / chunks, e = (item - n * chunks) * FR_THREADS + (int)threadIdx.x;
+        if (e >= E || (a.world_mask && !a.world_mask[e])) continue;
+        const int f = fr_clamp(a.out_frame[n], 0, M - 1), ref = fr_clamp(a.out_ref[n], -1, M - 1);
+        const FrFrame F = fr_frame(m, body_q, body_qd, a, f, e, vel);
+        const size_t row = (size_t)e * N + n;
+        if (a.transform) {
+            vec3 x = F.x;
+            quat q = F.q;
+            if (ref >= 0) {
+                const FrFrame R = fr_frame(m, body_q, body_qd, a, ref, e, false);
+                x = quat_rotate_inv(R.q, F.x - R.x);
+                q = quat_inverse(R.q) * F.q;
+            }
+            float* out = a.transform + 7 * row;
+            out[0] = x.x; out[1] = x.y; out[2] = x.z;
+            out[3] = q.x; out[4] = q.y; out[5] = q.z; out[6] = q.w;
+        }
+        if (a.velocity) {
+            const vec3 v = quat_rotate_inv(F.q, F.v), w = quat_rotate_inv(F.q, F.w);
+            float* out = a.velocity + 6 * row;
+            out[0] = v.x; out[1] = v.y; out[2] = v.z;
+            out[3] = w.x; out[4] = w.y; out[5] = w.z;
+        }
+        if (a.gravity_dir || a.accel) {
+            const vec3 g(m.gravity[e], m.gravity[ES + e], m.gravity[2 * ES + e]);
+            if (a.gravity_dir) {
+                const vec3 d = quat_rotate_inv(F.q, normalize(g));
+                float* out = a.gravity_dir + 3 * row;
+                out[0] = d.x; out[1] = d.y; out[2] = d.z;
+            }
+            if (a.accel) {
+                vec3 acc = -g;
+                if (F.body >= 0) {
+                    const vec3 dv = F.vc - fr_load3(prev_qd, 0, m.nb, F.body, ES, e);
+                    const vec3 dw = F.w - fr_load3(prev_qd, 3, m.nb, F.body, ES, e);
+                    acc = dv / dt + cross(dw / dt, F.r) + cross(F.w, cross(F.w, F.r)) - g;
+                }
+                acc = quat_rotate_inv(F.q, acc);
+                float* out = a.accel + 3 * row;
+                out[0] = acc.x; out[1] = acc.y; out[2] = acc.z;
+            }
+        }
     }
 }
 
@@ -1047,6 +1149,44 @@ nt_status nt_eval_ik_tile(const nt_model* m, const nt_state* in, float* joint_q,
 
 nt_status nt_eval_ik(const nt_model* m, const nt_state* in, float* joint_q, float* joint_qd, const uint8_t* art_mask, void* stream) {
     return nt_eval_ik_tile(m, in, joint_q, joint_qd, art_mask, 0, stream);
+}
+
+nt_status nt_frame_sensor(const nt_model* m, const nt_state* s, const nt_state* prev, float dt, const nt_frame_sensor_args* a, void* stream) {
+    if (!model_ok(m) || !s || !a || !s->body_q) return NT_ERR_INVALID_ARG;
+    if (a->frame_count <= 0 || a->out_count <= 0 || !a->frame_body || !a->frame_xform || !a->out_frame || !a->out_ref ||
+        !a->frame_body_host || !a->frame_xform_host || !a->out_frame_host || !a->out_ref_host)
+        return NT_ERR_INVALID_ARG;
+    if (!a->transform && !a->velocity && !a->gravity_dir && !a->accel) return NT_ERR_INVALID_ARG;
+    if ((a->velocity || a->accel) && (!s->body_qd || !m->body_param)) return NT_ERR_INVALID_ARG;
+    if ((a->gravity_dir || a->accel) && !m->gravity) return NT_ERR_INVALID_ARG;
+    if (a->accel && (!prev || !prev->body_qd || !(dt > 0.0f) || !(dt <= 3.0e38f))) return NT_ERR_INVALID_ARG;
+    const int M = a->frame_count, N = a->out_count;
+    for (int f = 0; f < M; ++f) {
+        if (a->frame_body_host[f] < -1 || a->frame_body_host[f] >= m->nb) return NT_ERR_INVALID_ARG;
+        const float* X = a->frame_xform_host + 7 * (size_t)f;
+        double qq = 0.0;
+        for (int k = 0; k < 7; ++k) {
+            if (!(X[k] >= -3.0e38f && X[k] <= 3.0e38f)) return NT_ERR_INVALID_ARG;  // (NaN fails both comparisons)
+            if (k >= 3) qq += (double)X[k] * (double)X[k];
+        }
+        const double norm_err = sqrt(qq) - 1.0;
+        if (!(norm_err >= -1.0e-4 && norm_err <= 1.0e-4)) return NT_ERR_INVALID_ARG;
+    }
+    for (int n = 0; n < N; ++n)
+        if (a->out_frame_host[n] < 0 || a->out_frame_host[n] >= M || a->out_ref_host[n] < -1 || a->out_ref_host[n] >= M)
+            return NT_ERR_INVALID_ARG;
+    // one wave per (row, 64 worlds); the item index stays an int
+    const long long chunks = ((long long)m->env_count + FR_THREADS - 1) / FR_THREADS, items = chunks * N;
+    if (items > 0x7fffffffLL) return NT_ERR_INVALID_ARG;
+#ifdef NT_EMULATED_GRID
+    const long long grid_cap = NT_EMULATED_GRID;
+#else
+    const long long grid_cap = FR_MAX_GRID;
+#endif
+    hipLaunchKernelGGL(frame_sensor_kernel, dim3((unsigned)(items < grid_cap ? items : grid_cap)), dim3(FR_THREADS), 0, (hipStream_t)stream,
+                       *m, (const float*)s->body_q, (const float*)s->body_qd, a->accel ? (const float*)prev->body_qd : (const float*)nullptr,
+                       dt, *a);
+    return hipGetLastError() == hipSuccess ? NT_OK : NT_ERR_LAUNCH;
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
 """Sensors.  ``SensorContact`` (further down): the net contact force per world on chosen bodies / shapes, split by counterpart.
+``SensorFrameTransform`` / ``SensorIMU`` (at the end): pose, velocity, projected gravity and specific force of sensor-owned frames.
 Ray-cast sensors: ``SensorRaycast`` casts R rays per world against the shapes of that world -- a height scan under a robot's base,
 a lidar sweep over the other bodies.  The capability of the reference's ``newton.sensors.SensorRaycast``; that one is a single
 camera, this one is ONE SENSOR PER WORLD of the replicated model, because that is what the batched layout serves: the same R rays
@@ -590,3 +591,238 @@ class SensorContact:
                                    contacts.force, self.slot_sensing, self.slot_counterpart, S, Cn, self.include_total, world_mask)
         sel = slice(None) if world_mask is None else np.asarray(_host_array(world_mask)).astype(bool).reshape(-1)
         self.net_force[sel] = out[sel]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# SensorFrameTransform / SensorIMU: pose, velocity, gravity direction and specific force of sensor-owned frames (nt_frame_sensor,
+# contract in include/newton_hip_kinematics.h)
+# ---------------------------------------------------------------------------------------------------------------------------------
+_QUAT_NORM_TOL = 1.0e-4  # nt_frame_sensor's own bound on | |q| - 1 | of a frame's local rotation
+
+
+def _world_gravity(model, dtype=np.float64):
+    """[E, 3]: the gravity row of every world, chosen as newton_amd.model.pack_param_arrays chooses nt_model.gravity."""
+    t = model.env
+    g = np.asarray(model.gravity, dtype=dtype).reshape(-1, 3)
+    world = np.asarray(model.body_world).reshape(t.env_count, t.nb)[:, 0] if t.nb else np.zeros(t.env_count, np.int64)
+    return g[world]
+
+
+def frame_sensor_numpy(model, body_q, body_qd, frame_body, frame_xform, out_frame, out_ref, body_qd_prev=None, dt=None, world_mask=None,
+                       dtype=np.float64, with_scale=False):
+    """The contract of nt_frame_sensor over Newton's flat AoS arrays (body_q [E * nb, 7], body_qd / body_qd_prev [E * nb, 6]): a dict
+    with ``transform`` [E, N, 7], ``velocity`` [E, N, 6], ``gravity_dir`` [E, N, 3] and ``accel`` [E, N, 3] in ``dtype`` (float64: the
+    reference the kernel is tested against, and the host-model path).  ``velocity`` is None without body_qd, ``accel`` without
+    body_qd_prev / dt.  Rows of worlds outside ``world_mask`` stay zero.  ``with_scale``: a fifth entry ``scale``, a dict of arrays that
+    broadcast against the four outputs -- per element the sum of the magnitudes of the terms the contract adds to form it (what a
+    rounding-error bound of the float32 kernel is proportional to)."""
+    t = model.env
+    E, nb = t.env_count, t.nb
+    fb = np.asarray(frame_body, dtype=np.int64).reshape(-1)
+    fx = np.asarray(_host_array(frame_xform), dtype=dtype).reshape(len(fb), 7)
+    of = np.asarray(out_frame, dtype=np.int64).reshape(-1)
+    orf = np.asarray(out_ref, dtype=np.int64).reshape(-1)
+    bq = np.asarray(_host_array(body_q), dtype=dtype).reshape(E, nb, 7)
+    att = fb >= 0
+    bi = np.where(att, fb, 0)
+    sel3 = att[None, :, None]
+    pl, ql = fx[None, :, :3], fx[None, :, 3:]
+    P, Q = bq[:, bi, :3], bq[:, bi, 3:]  # [E, M, ...]
+    x = np.where(sel3, P + _qrot(Q, pl), pl)
+    qf = np.where(sel3, _qmul(Q, ql), ql)
+    g = _world_gravity(model, dtype)  # [E, 3]
+    gn = np.linalg.norm(g, axis=-1, keepdims=True)
+    gdir = np.where(gn > 0.0, g / np.where(gn > 0.0, gn, 1.0), 0.0)
+    live = np.ones(E, bool) if world_mask is None else np.asarray(_host_array(world_mask)).astype(bool).reshape(E)
+    norm = lambda a: np.linalg.norm(a, axis=-1, keepdims=True)  # noqa: E731
+
+    # transform: X_ref^-1 X_frame
+    has_ref = (orf >= 0)[None, :, None]
+    ri = np.where(orf >= 0, orf, 0)
+    xr, qr = x[:, ri], qf[:, ri]
+    xm, qm = x[:, of], qf[:, of]
+    out = {"transform": np.concatenate([np.where(has_ref, _qrot(_qinv(qr), xm - xr), xm), np.where(has_ref, _qmul(_qinv(qr), qm), qm)],
+                                       axis=-1),
+           "velocity": None, "accel": None,
+           "gravity_dir": _qrot(_qinv(qm), np.broadcast_to(gdir[:, None, :], xm.shape))}
+    scale = {"transform": np.concatenate([np.broadcast_to(norm(xm) + np.where(has_ref, norm(xr), 0.0), xm.shape), np.ones_like(qm)], axis=-1),
+             "gravity_dir": np.ones(()), "velocity": None, "accel": None}
+    if body_qd is not None:
+        bqd = np.asarray(_host_array(body_qd), dtype=dtype).reshape(E, nb, 6)
+        com = np.asarray(model.body_com, dtype=dtype).reshape(E, nb, 3)
+        r = np.where(sel3, _qrot(Q, pl - com[:, bi]), 0.0)
+        vc, w = np.where(sel3, bqd[:, bi, :3], 0.0), np.where(sel3, bqd[:, bi, 3:], 0.0)
+        v = vc + np.cross(w, r)
+        out["velocity"] = np.concatenate([_qrot(_qinv(qm), v[:, of]), _qrot(_qinv(qm), w[:, of])], axis=-1)
+        s_lin = norm(vc) + norm(w) * norm(r)
+        # (the angular half adds nothing to w: its own magnitude bounds it, and never more than the linear half's scale is allowed)
+        scale["velocity"] = np.concatenate([np.broadcast_to(s_lin[:, of], xm.shape),
+                                            np.broadcast_to(np.minimum(s_lin, norm(w))[:, of], xm.shape)], axis=-1)
+        if body_qd_prev is not None:
+            if dt is None or not float(dt) > 0.0:
+                raise ValueError("frame_sensor_numpy: accel needs dt > 0, the time between the two states")
+            dt = float(dt)
+            pqd = np.asarray(_host_array(body_qd_prev), dtype=dtype).reshape(E, nb, 6)
+            vp, wp = np.where(sel3, pqd[:, bi, :3], 0.0), np.where(sel3, pqd[:, bi, 3:], 0.0)
+            acc = (vc - vp) / dt + np.cross((w - wp) / dt, r) + np.cross(w, np.cross(w, r)) - g[:, None, :]
+            out["accel"] = _qrot(_qinv(qm), acc[:, of])
+            s_acc = (norm(vc) + norm(vp) + (norm(w) + norm(wp)) * norm(r)) / dt + norm(w) ** 2 * norm(r) + gn[:, None, :]
+            scale["accel"] = np.broadcast_to(s_acc[:, of], xm.shape)
+    for k, v_ in out.items():
+        if v_ is not None:
+            out[k] = np.where(live[:, None, None], v_, 0.0).astype(dtype)
+    if with_scale:
+        out["scale"] = scale
+    return out
+
+
+class _FrameSensor:
+    """What SensorFrameTransform and SensorIMU share: the frame table, its checks, the resident outputs and the one launch."""
+
+    def _setup(self, model, table, out_frame, out_ref, outputs):
+        """table: [(body, xform or None)]; outputs: {name of the entry point's output: (attribute, components)} to allocate."""
+        name = type(self).__name__
+        if getattr(model, "is_heterogeneous", False):
+            raise NotImplementedError(f"{name}: heterogeneous models are unsupported (one sensor is N frames in every world of a replicated model)")
+        t = model.env
+        self.model = model
+        M = len(table)
+        self.frame_body = np.zeros(M, np.int32)
+        self.frame_xform = np.zeros((M, 7), np.float32)
+        for k, (body, xf) in enumerate(table):
+            body = int(body)
+            if not -1 <= body < t.nb:
+                raise ValueError(f"{name}: frame {k}: body {body} is out of range (env-local 0 .. {t.nb - 1}, or -1 for the world)")
+            xf = np.array([0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0]) if xf is None else np.asarray(_host_array(xf), dtype=np.float64).reshape(-1)
+            if xf.shape != (7,) or not np.all(np.isfinite(xf)):
+                raise ValueError(f"{name}: frame {k}: xform must be 7 finite numbers (p, q xyzw) or None")
+            if abs(np.linalg.norm(xf[3:]) - 1.0) > _QUAT_NORM_TOL:
+                raise ValueError(f"{name}: frame {k}: the quaternion of xform is not a unit quaternion (norm {np.linalg.norm(xf[3:]):.6g})")
+            self.frame_body[k], self.frame_xform[k] = body, xf
+        self.out_frame = np.ascontiguousarray(out_frame, dtype=np.int32)
+        self.out_ref = np.ascontiguousarray(out_ref, dtype=np.int32)
+        E, N = t.env_count, len(self.out_frame)
+        self._gpu = bool(getattr(model, "is_gpu", False))
+        self._out = {}
+        if self._gpu:
+            import torch  # noqa: PLC0415
+
+            from . import _lib  # noqa: PLC0415
+
+            dev = model.device_model().device
+            self._world_mask = torch.ones(E, dtype=torch.uint8, device=dev)
+            self._tables = [torch.from_numpy(x).to(dev) for x in (self.frame_body, self.frame_xform, self.out_frame, self.out_ref)]
+            a = _lib.nt_frame_sensor_args()
+            a.frame_count, a.out_count = M, N
+            a.frame_body, a.frame_xform, a.out_frame, a.out_ref = (x.data_ptr() for x in self._tables)
+            a.frame_body_host, a.frame_xform_host = self.frame_body.ctypes.data, self.frame_xform.ctypes.data
+            a.out_frame_host, a.out_ref_host = self.out_frame.ctypes.data, self.out_ref.ctypes.data
+            for key, ncomp in outputs.items():
+                self._out[key] = torch.zeros((E, N, ncomp), dtype=torch.float32, device=dev)
+                setattr(a, key, self._out[key].data_ptr())
+            self._args = a
+        else:
+            for key, ncomp in outputs.items():
+                self._out[key] = np.zeros((E, N, ncomp))
+
+    def _launch(self, state, state_prev, dt, world_mask):
+        name, t = type(self).__name__, self.model.env
+        if world_mask is not None and int(np.prod(np.shape(world_mask))) != t.env_count:
+            raise ValueError(f"world_mask must have {t.env_count} entries")
+        if self._gpu:
+            from . import _lib  # noqa: PLC0415
+            from .state import State  # noqa: PLC0415
+
+            if not isinstance(state, State) or not (state_prev is None or isinstance(state_prev, State)):
+                raise TypeError(f"{name}.eval: a GPU model needs State objects (body_q / body_qd are read on the device)")
+            dm = self.model.device_model()
+            if world_mask is not None:
+                import torch  # noqa: PLC0415
+
+                wm = world_mask if hasattr(world_mask, "data_ptr") else torch.from_numpy(np.asarray(world_mask).astype(np.uint8))
+                self._world_mask.copy_(wm.reshape(-1).to(torch.uint8))
+            self._args.world_mask = None if world_mask is None else self._world_mask.data_ptr()
+            d = state._desc()
+            dp = None if state_prev is None else state_prev._desc()
+            _lib.check(dm.lib.nt_frame_sensor(C.byref(dm.desc), C.byref(d), None if dp is None else C.byref(dp), float(dt), C.byref(self._args),
+                                              dm.stream()), "nt_frame_sensor")
+            return
+        got = frame_sensor_numpy(self.model, state.body_q, state.body_qd, self.frame_body, self.frame_xform, self.out_frame, self.out_ref,
+                                 None if state_prev is None else state_prev.body_qd, dt if state_prev is not None else None, world_mask)
+        sel = slice(None) if world_mask is None else np.asarray(_host_array(world_mask)).astype(bool).reshape(-1)
+        for key, dst in self._out.items():
+            dst[sel] = got[key][sel]
+
+
+class SensorFrameTransform(_FrameSensor):
+    """The pose of frames rigidly attached to bodies, relative to other such frames (the capability of the reference's
+    ``newton.sensors.SensorFrameTransform``): the four feet in the base frame.  The model has no sites, so the sensor owns its frames.
+
+    ``frames`` / ``reference_frames``: sequences of ``(body, xform)`` -- an env-local body 0 .. nb-1 (or -1: fixed in the world) and
+    the frame's transform in that body, 7 numbers (p, q xyzw) or None for the identity.  ``reference_frames`` has one entry per frame,
+    or one entry that serves every frame; None expresses the frames in the world.
+
+    ``eval(state)`` fills ``transforms`` [world, N, 7] = X_reference^-1 X_frame: a resident float32 tensor on a GPU model (one launch
+    of frame_sensor_kernel on the model's stream, no allocation, recordable by ``newton_amd.graph.capture``), a float64 numpy array on
+    a host model (``frame_sensor_numpy``).  Heterogeneous models: NotImplementedError."""
+
+    def __init__(self, model, frames, reference_frames=None):
+        frames = list(frames)
+        refs = [] if reference_frames is None else list(reference_frames)
+        N = len(frames)
+        if N == 0:
+            raise ValueError("SensorFrameTransform: no frame")
+        if reference_frames is not None and len(refs) not in (1, N):
+            raise ValueError(f"SensorFrameTransform: reference_frames must have 1 or {N} entries, got {len(refs)}")
+        out_ref = np.full(N, -1) if not refs else N + (np.arange(N) if len(refs) == N else np.zeros(N, np.int64))
+        self._setup(model, frames + refs, np.arange(N), out_ref, {"transform": 7})
+        self.transforms = self._out["transform"]
+
+    def eval(self, state, world_mask=None):
+        """Measure ``state.body_q``.  ``world_mask`` ([world] bool, numpy or torch): the rows of unselected worlds are neither computed
+        nor written.  GPU model: one kernel launch on the model's stream (the mask is copied into a resident buffer first)."""
+        self._launch(state, None, 0.0, world_mask)
+
+
+class SensorIMU(_FrameSensor):
+    """Accelerometer and gyroscope in body-attached frames (the capability of the reference's ``newton.sensors.SensorIMU``), and on
+    request the two proprioceptive terms locomotion policies take in the same frame.  ``frames``: as for SensorFrameTransform.
+
+    ``eval(state, state_prev, dt)`` fills, all in the frame's own axes and all [world, N, 3]:
+      ``accelerometer``      the specific force at the frame origin (a frame at rest reads -g: +|g| along the axis that points up);
+      ``gyroscope``          the angular velocity of the body;
+      ``linear_velocity``    (``want_velocity``) the velocity of the frame origin;
+      ``projected_gravity``  (``want_projected_gravity``) the unit gravity direction, zeros in a world without gravity.
+    ``gyroscope`` and ``linear_velocity`` are views of ``velocity`` [world, N, 6], not copies.
+
+    The model carries no ``body_qdd``, so the acceleration is the finite difference of the body velocities of two states the caller
+    already holds -- the ``state_in`` / ``state_out`` of a ``step`` or ``rollout``: ``state`` is the newer one, ``dt`` the time
+    between the two (after ``rollout(s0, s1, n)`` that is n times the substep).  The reading is therefore the MEAN acceleration over
+    that interval, not the reference's instantaneous ``body_qdd``; attitude, lever arm and the centripetal term are those of ``state``.
+    ``state_prev`` may be ``state`` itself: the centripetal term minus gravity.  Gravity is read from the model at every call: a
+    run-time ``set_gravity`` (after the solver's ``notify_model_changed``) takes effect without rebuilding the sensor.
+
+    GPU model: resident float32 tensors, one launch of frame_sensor_kernel on the model's stream per ``eval``, no allocation,
+    recordable by ``newton_amd.graph.capture``.  Host model: float64 numpy (``frame_sensor_numpy``).  Heterogeneous models:
+    NotImplementedError."""
+
+    def __init__(self, model, frames, want_velocity=False, want_projected_gravity=False):
+        frames = list(frames)
+        N = len(frames)
+        if N == 0:
+            raise ValueError("SensorIMU: no frame")
+        outputs = {"velocity": 6, "accel": 3}
+        if want_projected_gravity:
+            outputs["gravity_dir"] = 3
+        self._setup(model, frames, np.arange(N), np.full(N, -1), outputs)
+        self.velocity, self.accelerometer = self._out["velocity"], self._out["accel"]
+        self.gyroscope = self.velocity[..., 3:]
+        self.linear_velocity = self.velocity[..., :3] if want_velocity else None
+        self.projected_gravity = self._out.get("gravity_dir")
+
+    def eval(self, state, state_prev, dt, world_mask=None):
+        """``state``: the newer state, ``state_prev``: the older one, ``dt`` > 0: the time between them.  ``world_mask`` as for
+        SensorFrameTransform.eval."""
+        if not float(dt) > 0.0 or not np.isfinite(float(dt)):
+            raise ValueError(f"SensorIMU.eval: dt must be positive and finite (the time between the two states), got {dt}")
+        self._launch(state, state_prev, float(dt), world_mask)
