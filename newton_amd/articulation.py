@@ -495,14 +495,9 @@ def eval_ik(model, state, joint_q=None, joint_qd=None, mask=None, indices=None):
             raise TypeError("eval_ik: a GPU model needs a State (the body state is read on the device)")
         if t.nj == 0:
             return
-        art_mask = None
-        if art_sel is not None:
-            if t.na == 0 or t.na * t.env_count != art_sel.shape[0]:
-                raise NotImplementedError("eval_ik: mask / indices need articulations that cover every world's joints in order")
-            import torch  # noqa: PLC0415
-
-            art_mask = torch.from_numpy(art_sel.astype(np.uint8)).to(model.device_model().device)
-        _eval_ik_device(model, state, joint_q, joint_qd, art_mask)
+        if art_sel is not None and t.na == 0:
+            raise NotImplementedError("eval_ik: mask / indices need articulations that cover every world's joints in order")
+        _eval_ik_device(model, state, joint_q, joint_qd, _device_art_mask(model, art_sel, "eval_ik"))
         return
     jq, jqd = eval_ik_numpy(model, _host_array(state.body_q), _host_array(state.body_qd),
                             _host_array(state.joint_q if joint_q is None else joint_q),
@@ -810,10 +805,26 @@ def _mask_selection(model, mask, what):
     return art_sel
 
 
-def _group_slices(model, out, sizes, art_axis_dims):
-    """Per world group the slice of a global output that belongs to it (first axis), or None."""
-    edges = np.concatenate([[0], np.cumsum(sizes)])
-    return [None if out is None else out[edges[i]:edges[i + 1]] for i in range(len(sizes))]
+def _eval_jm_device(model, state, what, out, out_name, shape, aux, aux_name, aux_shape, art_sel):
+    """Device path of eval_jacobian / eval_mass_matrix (``what``): one launch of nt_<what> on the model's stream into ``out`` (the
+    caller's, checked, or a new tensor: zeroed first where a mask leaves slices unwritten) and the optional ``aux``.  Returns ``out``."""
+    import ctypes as C  # noqa: PLC0415
+
+    from . import _lib  # noqa: PLC0415
+
+    _articulated(model, what)
+    dm = model.device_model()
+    fresh = out is None
+    out = _device_out(model, out, shape, out_name)
+    if aux is not None:
+        aux = _device_out(model, aux, aux_shape, aux_name)
+    if fresh and art_sel is not None:
+        out.zero_()
+    art_mask = _device_art_mask(model, art_sel, what)
+    d = state._desc()
+    _lib.check(getattr(dm.lib, "nt_" + what)(C.byref(dm.desc), C.byref(d), out.data_ptr(), None if aux is None else aux.data_ptr(),
+                                             None if art_mask is None else art_mask.data_ptr(), dm.stream()), "nt_" + what)
+    return out
 
 
 def eval_jacobian(model, state, J=None, joint_S_s=None, mask=None):
@@ -837,23 +848,9 @@ def eval_jacobian(model, state, J=None, joint_S_s=None, mask=None):
     L, D = _art_dims(model)
     if not getattr(model, "is_gpu", False):
         return eval_jacobian_numpy(model, _host_array(state.body_q), _host_array(state.joint_q), J, joint_S_s, art_sel)
-    t = _articulated(model, "eval_jacobian")
-    import ctypes as C  # noqa: PLC0415
-
-    from . import _lib  # noqa: PLC0415
-
-    dm = model.device_model()
-    fresh = J is None
-    J = _device_out(model, J, (t.env_count * t.na, 6 * L, D), "J")
-    if joint_S_s is not None:
-        joint_S_s = _device_out(model, joint_S_s, (t.env_count * t.nd, 6), "joint_S_s")
-    if fresh and art_sel is not None:
-        J.zero_()
-    art_mask = _device_art_mask(model, art_sel, "eval_jacobian")
-    d = state._desc()
-    _lib.check(dm.lib.nt_eval_jacobian(C.byref(dm.desc), C.byref(d), J.data_ptr(), None if joint_S_s is None else joint_S_s.data_ptr(),
-                                       None if art_mask is None else art_mask.data_ptr(), dm.stream()), "nt_eval_jacobian")
-    return J
+    t = model.env
+    return _eval_jm_device(model, state, "eval_jacobian", J, "J", (t.env_count * t.na, 6 * L, D),
+                           joint_S_s, "joint_S_s", (t.env_count * t.nd, 6), art_sel)
 
 
 def eval_mass_matrix(model, state, H=None, J=None, body_I_s=None, joint_S_s=None, mask=None):
@@ -874,23 +871,9 @@ def eval_mass_matrix(model, state, H=None, J=None, body_I_s=None, joint_S_s=None
     D = _art_dims(model)[1]
     if not getattr(model, "is_gpu", False):
         return eval_mass_matrix_numpy(model, _host_array(state.body_q), _host_array(state.joint_q), H, body_I_s, art_sel)
-    t = _articulated(model, "eval_mass_matrix")
-    import ctypes as C  # noqa: PLC0415
-
-    from . import _lib  # noqa: PLC0415
-
-    dm = model.device_model()
-    fresh = H is None
-    H = _device_out(model, H, (t.env_count * t.na, D, D), "H")
-    if body_I_s is not None:
-        body_I_s = _device_out(model, body_I_s, (t.env_count * t.nb, 6, 6), "body_I_s")
-    if fresh and art_sel is not None:
-        H.zero_()
-    art_mask = _device_art_mask(model, art_sel, "eval_mass_matrix")
-    d = state._desc()
-    _lib.check(dm.lib.nt_eval_mass_matrix(C.byref(dm.desc), C.byref(d), H.data_ptr(), None if body_I_s is None else body_I_s.data_ptr(),
-                                          None if art_mask is None else art_mask.data_ptr(), dm.stream()), "nt_eval_mass_matrix")
-    return H
+    t = model.env
+    return _eval_jm_device(model, state, "eval_mass_matrix", H, "H", (t.env_count * t.na, D, D),
+                           body_I_s, "body_I_s", (t.env_count * t.nb, 6, 6), art_sel)
 
 
 def _eval_jm_groups(model, state, which, out, aux, art_sel):

@@ -2,6 +2,8 @@
 // nt_featherstone_kernels.hpp, their phases nt_featherstone.hpp (namespace ieee); this unit exists so that they are compiled with the
 // default scheduler (see nt_step_preamble.hpp).  eval_ik, eval_jacobian, eval_mass_matrix, ik_solve and frame_sensor (kernels and entry
 // points, include/newton_hip_kinematics.h) live here whole: the headers the stepping unit shares stay as they are.
+// Launch code: the solver's tile choice is fs_launch (a measured rule of its own); every kinematics entry point -- nt_eval_fk and the
+// four _tile entry points -- chooses its tile and launches through ONE function, kin_launch, below the kernels.
 #include "nt_step_preamble.hpp"
 #ifndef NT_EMULATED_GRID
 #include "../../include/newton_hip_kinematics.h"
@@ -983,6 +985,66 @@ __global__ void __launch_bounds__(256) ik_solve_kernel(KArgs a, nt_ik_problem P,
 }  // namespace ieee
 }  // namespace
 
+// ------------------------------------------------------------------------------------------------
+// kin_launch: the tile rule and the launch of every kinematics entry point (nt_eval_fk, nt_eval_ik_tile, nt_eval_jacobian_tile,
+// nt_eval_mass_matrix_tile, nt_ik_solve_tile).  envs_per_block 0: on replicated worlds (nt_model.params_uniform, UNI_OK) the
+// uniform-parameter tile of 16 -- ONE block-shared parameter copy, the parameters are four fifths of what the per-environment tile of
+// eval_ik reads -- if it fits the LDS, otherwise the widest per-environment-parameter tile of 16 / 8 / 4 / 1 that fits.  A named width:
+// that per-environment-parameter tile, if it is one of 1 / 4 / 8 / 16 and fits.  Nothing chosen: NT_ERR_UNSUPPORTED, nothing launched.
+// An entry point brings what differs: rows(uni), the floats per environment of its layout; shared_ints, its block-shared tables;
+// want, the slot-lanes of its widest phase (KArgs::nslot = min(want, 256 / epb)); launch(T, epb, lds_bytes), which returns
+// launch_tile(kernel<T>, a, epb, lds_bytes, stream, ...) for T = std::integral_constant of E or of 16 + NT_UNI.  UNI_OK is a template
+// argument: without it (nt_eval_fk) launch is never instantiated for 16 + NT_UNI, a kernel that entry point does not have.
+// ------------------------------------------------------------------------------------------------
+template <bool UNI_OK, typename Rows, typename Launch>
+static nt_status kin_launch(const nt_model* m, KArgs& a, int32_t envs_per_block, size_t shared_ints, int want, Rows&& rows, Launch&& launch) {
+    auto bytes = [&](int epb, bool uni) {
+        return tile_bytes(rows(uni), epb, shared_ints, uni ? make_layout(*m, false, false, true, false).uni_floats : 0);
+    };
+    const bool uni = UNI_OK && envs_per_block == 0 && m->params_uniform && bytes(16, true) <= LDS_BYTES_PER_CU;
+    int epb = 0;
+    if (uni) {
+        epb = 16;
+    } else if (envs_per_block == 0) {
+        const int cands[4] = {16, 8, 4, 1};
+        for (int i = 0; i < 4 && !epb; ++i)
+            if (bytes(cands[i], false) <= LDS_BYTES_PER_CU) epb = cands[i];
+    } else if ((envs_per_block == 1 || envs_per_block == 4 || envs_per_block == 8 || envs_per_block == 16) &&
+               bytes(envs_per_block, false) <= LDS_BYTES_PER_CU) {
+        epb = envs_per_block;
+    }
+    if (!epb) return NT_ERR_UNSUPPORTED;
+    const int cap = 256 / epb;
+    a.nslot = want < cap ? want : cap;
+    if constexpr (UNI_OK)
+        if (uni) return launch(std::integral_constant<int, 16 + NT_UNI>{}, 16, bytes(16, true));
+    return dispatch_epb(Epbs<16, 8, 4, 1>{}, epb, [&](auto E) { return launch(E, (int)E, bytes(E, false)); });
+}
+
+// nt_eval_jacobian_tile / nt_eval_mass_matrix_tile: argument checks and what they bring to kin_launch
+template <bool MASS>
+static nt_status jm_launch(const nt_model* m, const nt_state* in, float* out, float* aux, const uint8_t* art_mask, int32_t envs_per_block,
+                           hipStream_t stream) {
+    if (!model_ok(m) || !in || !in->body_q || !in->joint_q || !out) return NT_ERR_INVALID_ARG;
+    if (m->nj <= 0 || m->na <= 0 || !m->art_start || m->max_art_dofs < 0) return NT_ERR_UNSUPPORTED;
+#ifdef NT_DEV_FAST
+    return NT_ERR_UNSUPPORTED;
+#else
+    if (m->max_art_dofs == 0) return NT_OK;  // (no dofs: J and H have no entries)
+    KArgs a = {};
+    a.m = *m;
+    a.s_in = *in;
+    // slot-lanes: one per dof / joint / body (mass matrix: per entry of a dof's H row block); the streaming phase runs workgroup-wide
+    const int want = imax(imax(m->nb, m->nj), MASS ? m->nd * m->max_art_dofs : m->nd);
+    return kin_launch<true>(
+        m, a, envs_per_block, (size_t)topo_ints(*m) + jm_table_ints(*m), want, [&](bool uni) { return jm_layout(*m, uni, MASS).rows; },
+        [&](auto T, int epb, size_t lds_bytes) {
+            if constexpr (MASS) return launch_tile(eval_mass_matrix_kernel<T>, a, epb, lds_bytes, stream, out, aux, art_mask);
+            else return launch_tile(eval_jacobian_kernel<T>, a, epb, lds_bytes, stream, out, aux, art_mask);
+        });
+#endif
+}
+
 extern "C" {
 
 // shared launch logic of the Featherstone kernels (step / rollout)
@@ -1039,21 +1101,28 @@ static nt_status fs_launch(const nt_model* m, KArgs& a, int32_t envs_per_block, 
 
 static bool fs_state_ok(const nt_state* s) { return s && s->joint_q && s->joint_qd && s->body_q && s->body_qd; }
 
-nt_status nt_featherstone_step(const nt_model* m, const nt_featherstone_params* p, nt_state* s_in, nt_state* s_out,
-                                const nt_control* ctrl, const nt_contacts* c, float dt, int32_t envs_per_block, void* stream) {
-    if (!model_ok(m) || !p || !ctrl || !fs_state_ok(s_in) || !fs_state_ok(s_out)) return NT_ERR_INVALID_ARG;
-    if (m->nj <= 0 || m->na <= 0 || m->max_art_dofs < 0 || !m->art_start) return NT_ERR_UNSUPPORTED;
+// what nt_featherstone_step and nt_featherstone_rollout fill alike (contacts, has_contacts and substeps: the callers')
+static KArgs fs_args(const nt_model* m, const nt_featherstone_params* p, const nt_state* s_in, const nt_state* s_out, const nt_control* ctrl,
+                     float dt) {
     KArgs a = {};
     a.m = *m;
     a.s_in = *s_in;
     a.s_out = *s_out;
     a.c = *ctrl;
-    if (c) a.ct = *c;
-    a.has_contacts = (c != nullptr && m->np > 0) ? 1 : 0;
     a.sp.friction_smoothing = p->friction_smoothing;
     a.fp = *p;
     a.angular_damping = p->angular_damping;
     a.dt = dt;
+    return a;
+}
+
+nt_status nt_featherstone_step(const nt_model* m, const nt_featherstone_params* p, nt_state* s_in, nt_state* s_out,
+                                const nt_control* ctrl, const nt_contacts* c, float dt, int32_t envs_per_block, void* stream) {
+    if (!model_ok(m) || !p || !ctrl || !fs_state_ok(s_in) || !fs_state_ok(s_out)) return NT_ERR_INVALID_ARG;
+    if (m->nj <= 0 || m->na <= 0 || m->max_art_dofs < 0 || !m->art_start) return NT_ERR_UNSUPPORTED;
+    KArgs a = fs_args(m, p, s_in, s_out, ctrl, dt);
+    if (c) a.ct = *c;
+    a.has_contacts = (c != nullptr && m->np > 0) ? 1 : 0;
     return fs_launch(m, a, envs_per_block, false, (hipStream_t)stream);
 }
 
@@ -1063,17 +1132,9 @@ nt_status nt_featherstone_rollout(const nt_model* m, const nt_featherstone_param
     if (!model_ok(m) || !p || !ctrl || !c || !fs_state_ok(s0) || !fs_state_ok(s1) || !s0->body_f || !s1->body_f || substeps <= 0)
         return NT_ERR_INVALID_ARG;
     if (m->nj <= 0 || m->na <= 0 || m->max_art_dofs < 0 || !m->art_start) return NT_ERR_UNSUPPORTED;
-    KArgs a = {};
-    a.m = *m;
-    a.s_in = *s0;
-    a.s_out = *s1;
-    a.c = *ctrl;
+    KArgs a = fs_args(m, p, s0, s1, ctrl, dt);
     a.ct = *c;
     a.has_contacts = m->np > 0 ? 1 : 0;
-    a.sp.friction_smoothing = p->friction_smoothing;
-    a.fp = *p;
-    a.angular_damping = p->angular_damping;
-    a.dt = dt;
     a.substeps = substeps;
     return fs_launch(m, a, cp ? cp->envs_per_block : 0, true, (hipStream_t)stream);
 }
@@ -1083,6 +1144,7 @@ int32_t nt_featherstone_lds_bytes_per_env(const nt_model* m) {
     return make_fs_layout(*m, make_layout(*m, false, false, false, false)).rows * 4;  // (dense mass-matrix region, per-environment parameters: the largest form)
 }
 
+// the widest per-environment-parameter tile that fits (kin_launch without the uniform tile, no named width)
 nt_status nt_eval_fk(const nt_model* m, const float* joint_q, const float* joint_qd, nt_state* out, void* stream) {
     if (!model_ok(m) || !joint_q || !joint_qd || !out || !out->body_q || !out->body_qd) return NT_ERR_INVALID_ARG;
     if (m->nj <= 0) return NT_ERR_UNSUPPORTED;
@@ -1093,21 +1155,15 @@ nt_status nt_eval_fk(const nt_model* m, const float* joint_q, const float* joint
     a.m = *m;
     a.s_out = *out;
     const FsLayout F = make_fs_layout(*m, make_layout(*m, false, false, false, false), fs_tree_mode(a));  // (the kernel's own rule)
-    const size_t shared_ints = (size_t)topo_ints(*m) + fs_topo_ints(*m);
-    int epb = 0;
-    const int cands[4] = {16, 8, 4, 1};
-    for (int i = 0; i < 4 && !epb; ++i)
-        if (tile_bytes(F.rows, cands[i], shared_ints) <= LDS_BYTES_PER_CU) epb = cands[i];
-    if (!epb) return NT_ERR_UNSUPPORTED;
-    int want = imax(m->nb, m->nj), cap = 256 / epb;
-    a.nslot = want < cap ? want : cap;
-    return dispatch_epb(Epbs<16, 8, 4, 1>{}, epb, [&](auto E) {
-        return launch_tile(eval_fk_kernel<E>, a, E, tile_bytes(F.rows, E, shared_ints), (hipStream_t)stream, joint_q, joint_qd);
-    });
+    return kin_launch<false>(
+        m, a, 0, (size_t)topo_ints(*m) + fs_topo_ints(*m), imax(m->nb, m->nj), [&](bool) { return F.rows; },
+        [&](auto T, int epb, size_t lds_bytes) {
+            return launch_tile(eval_fk_kernel<T>, a, epb, lds_bytes, (hipStream_t)stream, joint_q, joint_qd);
+        });
 #endif
 }
 
-// widest tile that fits (0), or the per-environment-parameter tile of 1 / 4 / 8 / 16 environments the caller names
+// envs_per_block: the tile, by kin_launch's rule (0: the widest that fits; 1 / 4 / 8 / 16: that per-environment-parameter tile)
 nt_status nt_eval_ik_tile(const nt_model* m, const nt_state* in, float* joint_q, float* joint_qd, const uint8_t* art_mask,
                           int32_t envs_per_block, void* stream) {
     if (!model_ok(m) || !in || !in->body_q || !in->body_qd || !joint_q || !joint_qd) return NT_ERR_INVALID_ARG;
@@ -1118,32 +1174,11 @@ nt_status nt_eval_ik_tile(const nt_model* m, const nt_state* in, float* joint_q,
     KArgs a = {};
     a.m = *m;
     a.s_in = *in;
-    const size_t shared_ints = (size_t)topo_ints(*m);
-    auto bytes = [&](int epb, bool uni) {
-        return tile_bytes(ik_rows(*m, uni), epb, shared_ints, uni ? make_layout(*m, false, false, true, false).uni_floats : 0);
-    };
-    // replicated worlds (nt_model.params_uniform): ONE block-shared parameter copy -- the parameters are four fifths of what the
-    // per-environment tile reads
-    const bool uni = envs_per_block == 0 && m->params_uniform && bytes(16, true) <= LDS_BYTES_PER_CU;
-    int epb = 0;
-    if (uni) {
-        epb = 16;
-    } else if (envs_per_block == 0) {
-        const int cands[4] = {16, 8, 4, 1};
-        for (int i = 0; i < 4 && !epb; ++i)
-            if (bytes(cands[i], false) <= LDS_BYTES_PER_CU) epb = cands[i];
-    } else if ((envs_per_block == 1 || envs_per_block == 4 || envs_per_block == 8 || envs_per_block == 16) &&
-               bytes(envs_per_block, false) <= LDS_BYTES_PER_CU) {
-        epb = envs_per_block;
-    }
-    if (!epb) return NT_ERR_UNSUPPORTED;
-    const int want = imax(m->nb, m->nj), cap = 256 / epb;
-    a.nslot = want < cap ? want : cap;
-    if (uni)
-        return launch_tile(eval_ik_kernel<16 + NT_UNI>, a, 16, bytes(16, true), (hipStream_t)stream, joint_q, joint_qd, art_mask);
-    return dispatch_epb(Epbs<16, 8, 4, 1>{}, epb, [&](auto E) {
-        return launch_tile(eval_ik_kernel<E>, a, E, bytes(E, false), (hipStream_t)stream, joint_q, joint_qd, art_mask);
-    });
+    return kin_launch<true>(
+        m, a, envs_per_block, (size_t)topo_ints(*m), imax(m->nb, m->nj), [&](bool uni) { return ik_rows(*m, uni); },
+        [&](auto T, int epb, size_t lds_bytes) {
+            return launch_tile(eval_ik_kernel<T>, a, epb, lds_bytes, (hipStream_t)stream, joint_q, joint_qd, art_mask);
+        });
 #endif
 }
 
@@ -1189,54 +1224,7 @@ nt_status nt_frame_sensor(const nt_model* m, const nt_state* s, const nt_state* 
     return hipGetLastError() == hipSuccess ? NT_OK : NT_ERR_LAUNCH;
 }
 
-}  // extern "C"
-
-// shared launch code of nt_eval_jacobian_tile / nt_eval_mass_matrix_tile (tile rule: nt_eval_ik_tile's)
-template <bool MASS>
-static nt_status jm_launch(const nt_model* m, const nt_state* in, float* out, float* aux, const uint8_t* art_mask, int32_t envs_per_block,
-                           hipStream_t stream) {
-    if (!model_ok(m) || !in || !in->body_q || !in->joint_q || !out) return NT_ERR_INVALID_ARG;
-    if (m->nj <= 0 || m->na <= 0 || !m->art_start || m->max_art_dofs < 0) return NT_ERR_UNSUPPORTED;
-#ifdef NT_DEV_FAST
-    return NT_ERR_UNSUPPORTED;
-#else
-    if (m->max_art_dofs == 0) return NT_OK;  // (no dofs: J and H have no entries)
-    KArgs a = {};
-    a.m = *m;
-    a.s_in = *in;
-    const size_t shared_ints = (size_t)topo_ints(*m) + jm_table_ints(*m);
-    auto bytes = [&](int epb, bool uni) {
-        return tile_bytes(jm_layout(*m, uni, MASS).rows, epb, shared_ints, uni ? make_layout(*m, false, false, true, false).uni_floats : 0);
-    };
-    const bool uni = envs_per_block == 0 && m->params_uniform && bytes(16, true) <= LDS_BYTES_PER_CU;
-    int epb = 0;
-    if (uni) {
-        epb = 16;
-    } else if (envs_per_block == 0) {
-        const int cands[4] = {16, 8, 4, 1};
-        for (int i = 0; i < 4 && !epb; ++i)
-            if (bytes(cands[i], false) <= LDS_BYTES_PER_CU) epb = cands[i];
-    } else if ((envs_per_block == 1 || envs_per_block == 4 || envs_per_block == 8 || envs_per_block == 16) &&
-               bytes(envs_per_block, false) <= LDS_BYTES_PER_CU) {
-        epb = envs_per_block;
-    }
-    if (!epb) return NT_ERR_UNSUPPORTED;
-    // slot-lanes: one per dof / joint / body (mass matrix: per entry of a dof's H row block); the streaming phase runs workgroup-wide
-    const int want = imax(imax(m->nb, m->nj), MASS ? m->nd * m->max_art_dofs : m->nd), cap = 256 / epb;
-    a.nslot = want < cap ? want : cap;
-    if (uni) {
-        if constexpr (MASS) return launch_tile(eval_mass_matrix_kernel<16 + NT_UNI>, a, 16, bytes(16, true), stream, out, aux, art_mask);
-        else return launch_tile(eval_jacobian_kernel<16 + NT_UNI>, a, 16, bytes(16, true), stream, out, aux, art_mask);
-    }
-    return dispatch_epb(Epbs<16, 8, 4, 1>{}, epb, [&](auto E) {
-        if constexpr (MASS) return launch_tile(eval_mass_matrix_kernel<E>, a, E, bytes(E, false), stream, out, aux, art_mask);
-        else return launch_tile(eval_jacobian_kernel<E>, a, E, bytes(E, false), stream, out, aux, art_mask);
-    });
-#endif
-}
-
-extern "C" {
-
+// envs_per_block: the tile, by kin_launch's rule (jm_launch)
 nt_status nt_eval_jacobian_tile(const nt_model* m, const nt_state* in, float* J, float* joint_S_s, const uint8_t* art_mask,
                                 int32_t envs_per_block, void* stream) {
     return jm_launch<false>(m, in, J, joint_S_s, art_mask, envs_per_block, (hipStream_t)stream);
@@ -1246,6 +1234,7 @@ nt_status nt_eval_jacobian(const nt_model* m, const nt_state* in, float* J, floa
     return nt_eval_jacobian_tile(m, in, J, joint_S_s, art_mask, 0, stream);
 }
 
+// envs_per_block: the tile, by kin_launch's rule (jm_launch)
 nt_status nt_eval_mass_matrix_tile(const nt_model* m, const nt_state* in, float* H, float* body_I_s, const uint8_t* art_mask,
                                    int32_t envs_per_block, void* stream) {
     return jm_launch<true>(m, in, H, body_I_s, art_mask, envs_per_block, (hipStream_t)stream);
@@ -1255,7 +1244,7 @@ nt_status nt_eval_mass_matrix(const nt_model* m, const nt_state* in, float* H, f
     return nt_eval_mass_matrix_tile(m, in, H, body_I_s, art_mask, 0, stream);
 }
 
-// nt_ik_solve: tile rule as nt_eval_ik_tile's
+// envs_per_block: the tile, by kin_launch's rule
 nt_status nt_ik_solve_tile(const nt_model* m, const nt_ik_problem* p, const float* joint_q_in, float* joint_q_out, float* lambda, float* cost,
                            int32_t iterations, float step_size, int32_t envs_per_block, void* stream) {
     if (!model_ok(m) || !p || !joint_q_in || !joint_q_out || !lambda || !cost || iterations < 0 || p->count < 0) return NT_ERR_INVALID_ARG;
@@ -1271,33 +1260,14 @@ nt_status nt_ik_solve_tile(const nt_model* m, const nt_ik_problem* p, const floa
 #else
     KArgs a = {};
     a.m = *m;
-    const size_t shared_ints = (size_t)topo_ints(*m) + iks_table_ints(*m);
-    auto bytes = [&](int epb, bool uni) {
-        return tile_bytes(iks_layout(*m, *p, uni).rows, epb, shared_ints, uni ? make_layout(*m, false, false, true, false).uni_floats : 0);
-    };
-    const bool uni = envs_per_block == 0 && m->params_uniform && bytes(16, true) <= LDS_BYTES_PER_CU;
-    int epb = 0;
-    if (uni) {
-        epb = 16;
-    } else if (envs_per_block == 0) {
-        const int cands[4] = {16, 8, 4, 1};
-        for (int i = 0; i < 4 && !epb; ++i)
-            if (bytes(cands[i], false) <= LDS_BYTES_PER_CU) epb = cands[i];
-    } else if ((envs_per_block == 1 || envs_per_block == 4 || envs_per_block == 8 || envs_per_block == 16) &&
-               bytes(envs_per_block, false) <= LDS_BYTES_PER_CU) {
-        epb = envs_per_block;
-    }
-    if (!epb) return NT_ERR_UNSUPPORTED;
     // slot-lanes: one per entry of the normal equations (the widest phase)
-    const int want = imax(imax(m->nb, m->nj), m->nd * (m->nd + 1) / 2 + m->nd), cap = 256 / epb;
-    a.nslot = want < cap ? want : cap;
-    if (uni)
-        return launch_tile(ik_solve_kernel<16 + NT_UNI>, a, 16, bytes(16, true), (hipStream_t)stream, *p, joint_q_in, joint_q_out, lambda, cost,
-                           (int)iterations, step_size);
-    return dispatch_epb(Epbs<16, 8, 4, 1>{}, epb, [&](auto E) {
-        return launch_tile(ik_solve_kernel<E>, a, E, bytes(E, false), (hipStream_t)stream, *p, joint_q_in, joint_q_out, lambda, cost,
-                           (int)iterations, step_size);
-    });
+    const int want = imax(imax(m->nb, m->nj), m->nd * (m->nd + 1) / 2 + m->nd);
+    return kin_launch<true>(
+        m, a, envs_per_block, (size_t)topo_ints(*m) + iks_table_ints(*m), want, [&](bool uni) { return iks_layout(*m, *p, uni).rows; },
+        [&](auto T, int epb, size_t lds_bytes) {
+            return launch_tile(ik_solve_kernel<T>, a, epb, lds_bytes, (hipStream_t)stream, *p, joint_q_in, joint_q_out, lambda, cost,
+                               (int)iterations, step_size);
+        });
 #endif
 }
 
