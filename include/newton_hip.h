@@ -281,8 +281,14 @@ nt_status nt_featherstone_rollout(const nt_model* m, const nt_featherstone_param
 nt_status nt_xpbd_rollout(const nt_model* m, const nt_xpbd_params* p, const nt_collide_params* cp, nt_state* s0,
                           nt_state* s1, const nt_control* ctrl, nt_contacts* c, float dt, int32_t substeps, void* stream);
 /* The launch shape nt_xpbd_rollout would take for this model: out = {environments per workgroup, workgroup size, minimum
- * waves per SIMD, uniform-parameter tile (nt_model.params_uniform), bit 0 convex code present | bit 1 pair-heavy tile};
- * the kernel is xpbd_rollout_kernel<out[0] + 256 * out[3], convex, pair-heavy, out[1], out[2]> (profilers print that name) */
+ * waves per SIMD, uniform-parameter tile (nt_model.params_uniform), bit 0 convex code present | bit 1 pair-heavy tile |
+ * bit 2 (value 4) the specialised instance of the uniform tile of 16: the facts the launch code has verified for this model and these
+ * solver options -- contact records and live list in LDS, integrate_bodies beside the pairs, split body lanes, no restitution /
+ * velocity-from-delta pass, contacts, joints and iterations present -- are compile-time constants of the kernel.  Same results
+ * bit for bit; NT_XPBD_CFG="epb,threads,minw,uni,cvx,spec" with spec = 0 forces the generic instance, 1 asks for the specialised
+ * one and is refused (NT_ERR_UNSUPPORTED at launch) where a fact does not hold};
+ * the kernel is xpbd_rollout_kernel<out[0] + 256 * out[3] + 512 * (bit 2), convex, pair-heavy, out[1], out[2]> (profilers print that
+ * name) */
 nt_status nt_xpbd_rollout_shape(const nt_model* m, const nt_xpbd_params* p, const nt_collide_params* cp, int32_t out[5]);
 
 /* -------- boundary helpers -------- */

@@ -539,7 +539,10 @@ NT_DI void phase_pair_eval(const Ctx<EPB>& c) {
 // in LDS (atomic counter, zeroed during the shape phase; the order of the list is irrelevant, every pair owns its slots);
 // misses retire here.  Stage 2 deals the hits densely to the lanes: one pass of the narrow phase instead of ceil(np / lanes).
 template <int EPB>
-NT_DI bool pairs_compacted(const Ctx<EPB>& c) { return !c.big && c.a.m.np > c.nslot; }
+NT_DI bool pairs_compacted(const Ctx<EPB>& c) {
+    if constexpr (Ctx<EPB>::SPEC) return false;  // (np <= nslot: verified by the launch code)
+    else return !c.big && c.a.m.np > c.nslot;
+}
 template <int EPB>
 NT_DI void phase_pair_broad_staged(const Ctx<EPB>& c) {
     if (!c.valid) return;

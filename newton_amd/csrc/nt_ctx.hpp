@@ -4,10 +4,25 @@
 // The tile code EPB of every kernel template carries the environments per workgroup in its low byte and the
 // uniform-parameter flag NT_UNI in bit 8: Ctx<EPB>::N is the count, Ctx<EPB>::UNI the flag.
 constexpr int NT_UNI = 256;
+// Bit 9, NT_SPEC (fused XPBD rollout only): the launch code has verified every fact of xpbd_spec_tile_fits (nt_kernels.hip) for this
+// model, these solver options and the granted tile extras, so the kernel takes them as constants instead of testing them in every
+// barrier interval: contact records and live list in LDS, pose snapshot granted (integrate_bodies beside the pairs), body phases on
+// linear / angular lanes, one pass of uncompacted pairs, no restitution / velocity-from-delta, contacts, joints and iterations present.
+// Model sizes, joint types, body flags, iteration count and every float stay run-time values.  Ctx<EPB>::SPEC is the flag.
+constexpr int NT_SPEC = 512;
+#ifndef NT_ASSUME  // a fact the launch code verified, stated to the optimiser (nothing where the compiler has no such builtin)
+#if defined(__clang__)
+#define NT_ASSUME(x) __builtin_assume(x)
+#else
+#define NT_ASSUME(x) ((void)0)
+#endif
+#endif
 template <int EPB>
 struct Ctx {
     static constexpr int N = EPB & 255;
     static constexpr bool UNI = (EPB & NT_UNI) != 0;
+    static constexpr bool SPEC = (EPB & NT_SPEC) != 0;
+    static constexpr int SPW = 64 / N > 0 ? 64 / N : 1;  // slots per wave
     const KArgs& a;
     Topo T;
     float* lds;
@@ -29,6 +44,9 @@ struct Ctx {
     bool big;  // contact records in HBM, manifold polygon scratch per lane (compile-time constant at every construction site)
     int ES;
     bool valid;
+    // launch-invariant slot ranges (first slot of the second population of a shared interval, on a wave boundary), computed once here
+    // instead of in every barrier interval.  Read by the NT_SPEC instance only; everywhere else the phases derive them in place
+    struct Ranges { int B0, S0, I0, A0; } R;  // linear body lanes, joint-force lanes, integrate lanes, angular joint lanes
 
     // rows: float rows per env in front of the block-shared topology ints (-1: the XPBD / collide layout)
     NT_DI Ctx(const KArgs& a_, float* lds_, int rows = -1, const bool big_ = false) : a(a_), lds(lds_), big(big_) {
@@ -49,6 +67,7 @@ struct Ctx {
         valid = env < a.m.env_count && slot < nslot;
         tslot = slot;
         const nt_model& m = a.m;
+        R = {wave_up(m.nb), wave_up(m.ns), wave_up(m.np), wave_up(m.nj)};
         int* ti = reinterpret_cast<int*>(lds + (size_t)rows * N);
         int o = 0;
         // The 24 env-uniform tables are fetched FIRST -- every thread one element of each, all loads in flight together -- and
@@ -113,7 +132,8 @@ struct Ctx {
     NT_DI explicit Ctx(const OtherCtx& o, int /*tag*/)
         : a(o.a), T(o.T), lds(o.lds), up(o.up), L(o.L), e(o.e), slot(o.slot), env(o.env), nslot(o.nslot), tslot(o.tslot),
           pose_in_off(o.pose_in_off), lane_split(o.lane_split), gworld_ready(o.gworld_ready), lds_records(o.lds_records), hbm_out(o.hbm_out), aos_records(o.aos_records), big(o.big),
-          ES(o.ES), valid(o.valid) {}
+          ES(o.ES), valid(o.valid), R{o.R.B0, o.R.S0, o.R.I0, o.R.A0} {}
+    static NT_DI int wave_up(int n) { return ((n + SPW - 1) / SPW) * SPW; }  // n rounded up to whole waves of slots
     // LDS element (comp, s) of a slot-major field.  `n` (the slot count of the [comp][n] HBM twin) is not needed here; the
     // argument stays so that every access reads like its global-memory counterpart g(comp, n, s)
     template <int NC>

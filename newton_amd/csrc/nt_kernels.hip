@@ -242,8 +242,8 @@ int narrow_semi_epb(const nt_model& m, int epb, int rows) {
 // semi: the SolverSemiImplicit kernel (own scratch layout); max_threads: the kernel's THREADS template argument
 // a.tile_opts on entry: the NT_TILE_* layout extras the kernel can use (nt_xpbd_rollout asks); granted only while the tile still fits
 // the CU, and the kernel sees what was granted
-template <typename K>
-nt_status launch(K kernel, KArgs a, int epb, hipStream_t stream, int max_threads = 0, bool semi = false, bool uni = false) {
+// grant_tile: the host's decisions for one tile launch -- a.tile_opts (granted), a.nslot -- and the tile's LDS bytes; false: no fit
+bool grant_tile(KArgs& a, int epb, int max_threads, bool semi, bool uni, size_t& lds_bytes) {
     int tile_opts = a.tile_opts;
     auto opts_bytes = [&](int opts) {
         LdsLayout Lo = make_layout_host(a.m, xpbd_keeps_prestep_state(a.p), uni, opts, NT_BIG_SCENE_LANES);
@@ -264,8 +264,13 @@ nt_status launch(K kernel, KArgs a, int epb, hipStream_t stream, int max_threads
     const int big_lanes =
         a.m.contact_scratch_in_hbm && tile_threads(a.nslot, epb) > NT_BIG_SCENE_LANES ? NT_BIG_SCENE_LANES_WIDE : NT_BIG_SCENE_LANES;
     LdsLayout L = make_layout_host(a.m, xpbd_keeps_prestep_state(a.p), uni, tile_opts, big_lanes);
-    const size_t lds_bytes = tile_bytes(semi ? L.rows_semi : L.rows_per_env, epb, topo_ints(a.m), L.uni_floats);
-    if (lds_bytes > LDS_BYTES_PER_CU) return NT_ERR_UNSUPPORTED;
+    lds_bytes = tile_bytes(semi ? L.rows_semi : L.rows_per_env, epb, topo_ints(a.m), L.uni_floats);
+    return lds_bytes <= LDS_BYTES_PER_CU;
+}
+template <typename K>
+nt_status launch(K kernel, KArgs a, int epb, hipStream_t stream, int max_threads = 0, bool semi = false, bool uni = false) {
+    size_t lds_bytes;
+    if (!grant_tile(a, epb, max_threads, semi, uni, lds_bytes)) return NT_ERR_UNSUPPORTED;
     return launch_tile(kernel, a, epb, lds_bytes, stream);
 }
 
@@ -295,31 +300,38 @@ nt_status dispatch_collide_epb(const nt_model& m, int epb, F&& f) {
 }
 
 // Launch shape of the analytic (non-convex) fused XPBD rollout: environments per workgroup, workgroup size, minimum waves
-// per SIMD (register cap), uniform-parameter tile.  NT_XPBD_CFG="epb,threads,minw[,uni]" selects one of the compiled shapes
-// for A/B measurements.
-struct XpbdCfg { int epb, threads, minw, uni, cvx; };
-inline bool xpbd_cfg_override(XpbdCfg& c) {
+// per SIMD (register cap), uniform-parameter tile.  NT_XPBD_CFG="epb,threads,minw[,uni[,cvx[,spec]]]" selects one of the compiled
+// shapes for A/B measurements; spec: 0 forces the generic instance of the shape, 1 asks for the specialised one (NT_SPEC; refused
+// where xpbd_spec_tile_fits does not hold), absent: the dispatch decides.
+// XpbdCfg::spec is the decision: 1 = the NT_SPEC instance runs.
+struct XpbdCfg { int epb, threads, minw, uni, cvx, spec; };
+inline bool xpbd_cfg_override(XpbdCfg& c, int& spec_request) {
     const char* e = getenv("NT_XPBD_CFG");
     if (!e) return false;
-    c.uni = c.cvx = 0;
-    return sscanf(e, "%d,%d,%d,%d,%d", &c.epb, &c.threads, &c.minw, &c.uni, &c.cvx) >= 3;
+    c.uni = c.cvx = c.spec = 0;
+    spec_request = -1;
+    return sscanf(e, "%d,%d,%d,%d,%d,%d", &c.epb, &c.threads, &c.minw, &c.uni, &c.cvx, &spec_request) >= 3;
 }
+// The U column of a shape is its tile-code flags over NT_UNI: 1 the uniform-parameter tile, 1 + NT_SPEC_U the same tile with the
+// host-verified facts of xpbd_spec_tile_fits compiled in (NT_SPEC) -- that one shape only: 16 environments, analytic pairs.
+#define NT_SPEC_U (NT_SPEC / NT_UNI)
 // Shapes the default dispatch can take are always compiled; the A/B shapes (NT_XPBD_CFG experiments, tests/test_uniform_tile.py on
 // the emulated library) only with -DNT_ALL_SHAPES: each fused-rollout instantiation costs ~25 s of hipcc time.
 #ifdef NT_ALL_SHAPES
 #define NT_XPBD_ROLLOUT_SHAPES(X) \
     X(16, 512, 1, 0) X(16, 256, 1, 0) X(8, 256, 2, 0) \
-    X(16, 256, 2, 1) X(16, 512, 1, 1) X(16, 512, 2, 1) X(16, 512, 4, 1) X(32, 512, 1, 1) X(8, 128, 4, 1) X(8, 256, 4, 1)
+    X(16, 256, 2, 1) X(16, 512, 1, 1) X(16, 512, 2, 1) X(16, 512, 4, 1) X(32, 512, 1, 1) X(8, 128, 4, 1) X(8, 256, 4, 1) \
+    X(16, 512, 1, 1 + NT_SPEC_U)
 #define NT_XPBD_ROLLOUT_SHAPES_CVX(X) X(8, 256, 2, 1) X(16, 512, 1, 1) X(16, 256, 2, 1)
 #elif defined(NT_DEV_FAST)
-#define NT_XPBD_ROLLOUT_SHAPES(X) X(16, 512, 1, 0) X(32, 512, 1, 1) X(16, 512, 1, 1)
+#define NT_XPBD_ROLLOUT_SHAPES(X) X(16, 512, 1, 0) X(32, 512, 1, 1) X(16, 512, 1, 1) X(16, 512, 1, 1 + NT_SPEC_U)
 #ifdef NT_DEV_CVX  // (+ the convex uniform tile of 16: the 8-box stacks and the box-foot quadruped)
 #define NT_XPBD_ROLLOUT_SHAPES_CVX(X) X(16, 512, 1, 1)
 #else
 #define NT_XPBD_ROLLOUT_SHAPES_CVX(X)
 #endif
 #else
-#define NT_XPBD_ROLLOUT_SHAPES(X) X(16, 512, 1, 0) X(32, 512, 1, 1) X(16, 512, 1, 1)
+#define NT_XPBD_ROLLOUT_SHAPES(X) X(16, 512, 1, 0) X(32, 512, 1, 1) X(16, 512, 1, 1) X(16, 512, 1, 1 + NT_SPEC_U)
 #define NT_XPBD_ROLLOUT_SHAPES_CVX(X) X(8, 256, 2, 1) X(16, 512, 1, 1)
 #endif
 // convex (MPR / GJK) variants of the uniform-parameter tile: the parameter diet lets two 8-environment workgroups (or one of 16)
@@ -327,11 +339,13 @@ inline bool xpbd_cfg_override(XpbdCfg& c) {
 // the shape uniform-parameter models run by default once there are enough environments to give every CU a tile of 32 (measured,
 // MI355X, quadruped: 4096 envs 78 vs 92 M env-steps/s for the 16-env per-environment tile -- half the CUs idle; 8192 envs 158
 // vs 101 M; 65536 envs 157 vs 99 M.  2 x (16, 256) per CU: 144-149 M)
-constexpr XpbdCfg NT_XPBD_UNI_DEFAULT = {32, 512, 1, 1, 0};
+constexpr XpbdCfg NT_XPBD_UNI_DEFAULT = {32, 512, 1, 1, 0, 0};
 // ... and below that size: the uniform tile of 16 (one per CU up to 4 096 environments).  Same kernels as the per-environment tile with
 // the parameters read by broadcast from one block-shared copy: 3 % faster at 4 096 environments (profiles/r05c_ab.txt), and the 89 KB of
 // LDS it leaves free hold the tile extras of the fused rollout (NT_TILE_*)
-constexpr XpbdCfg NT_XPBD_UNI_SMALL = {16, 512, 1, 1, 0};
+constexpr XpbdCfg NT_XPBD_UNI_SMALL = {16, 512, 1, 1, 0, 0};
+// ... whose NT_SPEC instance the dispatch takes by itself wherever xpbd_spec_tile_fits holds
+constexpr bool NT_XPBD_SPEC_DEFAULT = true;
 // the analytic rollout shape of a uniform-parameter model (false: the per-environment tiles)
 inline bool pick_uni_shape(const nt_model& m, bool rest, const nt_collide_params* cp, XpbdCfg& c) {
     if (!m.params_uniform || rest || (cp != nullptr && cp->envs_per_block != 0)) return false;
@@ -341,8 +355,8 @@ inline bool pick_uni_shape(const nt_model& m, bool rest, const nt_collide_params
 }
 nt_status launch_xpbd_rollout_shape(const KArgs& a, XpbdCfg c, hipStream_t stream) {
 #define X(E, T, W, U) \
-    if (!c.cvx && c.epb == E && c.threads == T && c.minw == W && c.uni == U) \
-        return launch(xpbd_rollout_kernel<E + U * NT_UNI, false, false, T, W>, a, E, stream, T, false, U != 0);
+    if (!c.cvx && c.epb == E && c.threads == T && c.minw == W && c.uni + c.spec * NT_SPEC_U == (U)) \
+        return launch(xpbd_rollout_kernel<E + (U) * NT_UNI, false, false, T, W>, a, E, stream, T, false, (U) != 0);
     NT_XPBD_ROLLOUT_SHAPES(X)
 #undef X
 #define X(E, T, W, U) \
@@ -355,8 +369,8 @@ nt_status launch_xpbd_rollout_shape(const KArgs& a, XpbdCfg c, hipStream_t strea
 // convex models with uniform parameters: the widest uniform tile that fits, once every CU gets at least two of the narrow ones
 inline bool pick_cvx_uni_shape(const nt_model& m, bool rest, XpbdCfg& c) {
     if (!m.params_uniform || rest || m.contact_scratch_in_hbm) return false;
-    if (m.env_count >= 256 * 16 && tile_lds_bytes(m, 16, rest, true) <= LDS_BYTES_PER_CU) { c = {16, 512, 1, 1, 1}; return true; }
-    if (m.env_count >= 256 * 16 && 2 * tile_lds_bytes(m, 8, rest, true) <= LDS_BYTES_PER_CU) { c = {8, 256, 2, 1, 1}; return true; }
+    if (m.env_count >= 256 * 16 && tile_lds_bytes(m, 16, rest, true) <= LDS_BYTES_PER_CU) { c = {16, 512, 1, 1, 1, 0}; return true; }
+    if (m.env_count >= 256 * 16 && 2 * tile_lds_bytes(m, 8, rest, true) <= LDS_BYTES_PER_CU) { c = {8, 256, 2, 1, 1, 0}; return true; }
     return false;
 }
 
@@ -367,26 +381,70 @@ enum class XpbdRoute {
     tile,     // c.epb environments per workgroup on the per-environment tiles (pair-heavy models: c.threads lanes)
     shape,    // c: one of the compiled shapes (launch_xpbd_rollout_shape)
 };
-XpbdRoute plan_xpbd_rollout(const nt_model& m, bool rest, const nt_collide_params* cp, XpbdCfg& c) {
+// what nt_xpbd_rollout hands its kernel, as far as model and solver options decide it (states, control and Contacts follow there)
+KArgs xpbd_rollout_args(const nt_model& m, const nt_xpbd_params& p, float dt, int substeps) {
+    KArgs a = {};
+    a.m = m;
+    a.has_contacts = m.np > 0 ? 1 : 0;
+    a.p = p;
+    a.angular_damping = p.angular_damping;
+    a.dt = dt;
+    a.substeps = substeps;
+    a.tile_opts = NT_TILE_POSE_SNAPSHOT | NT_TILE_LDS_RECORDS;  // (request; grant_tile grants what the tile has room for)
+    return a;
+}
+// May shape c of this launch run its NT_SPEC instance?  Every fact that instance takes as a constant (nt_ctx.hpp: NT_SPEC; the
+// `if constexpr (SPEC)` sites of nt_xpbd_kernels.hpp / nt_xpbd.hpp / nt_collide.hpp) is checked HERE and nowhere else, from the
+// model, the solver options, the Contacts and the tile extras / slot lanes grant_tile settles on for this very launch.
+bool xpbd_spec_tile_fits(const KArgs& a, const XpbdCfg& c) {
+    const nt_model& m = a.m;
+    // the one compiled instance: the analytic uniform-parameter tile of 16 (the template asserts the same)
+    if (c.cvx || c.epb != NT_XPBD_UNI_SMALL.epb || c.threads != NT_XPBD_UNI_SMALL.threads || c.minw != NT_XPBD_UNI_SMALL.minw || c.uni != 1)
+        return false;
+    if (!m.params_uniform || m.contact_scratch_in_hbm || m.np_analytic != m.np) return false;  // uniform tile, staged, no convex pairs
+    if (a.ct.flat.row_start) return false;                                                      // no rows of the SDF legs
+    if (xpbd_keeps_prestep_state(a.p)) return false;               // enable_restitution == 0, velocity-from-delta == 0
+    if (!a.has_contacts || m.np <= 0 || m.nj <= 0 || a.p.iterations <= 0) return false;  // contact and joint phases run, an apply follows
+    KArgs g = a;
+    size_t lds_bytes;
+    if (!grant_tile(g, c.epb, c.threads, false, true, lds_bytes)) return false;
+    // contact records + live list in LDS (lds_records, L.has_lt; hbm_out = last substep), pose snapshot rows in the layout
+    if ((g.tile_opts & (NT_TILE_POSE_SNAPSHOT | NT_TILE_LDS_RECORDS)) != (NT_TILE_POSE_SNAPSHOT | NT_TILE_LDS_RECORDS)) return false;
+    if (!make_layout_host(m, false, true, g.tile_opts).has_lt) return false;
+    const int spw = 64 / c.epb, nslot = g.nslot;
+    auto wave_up = [&](int n) { return ((n + spw - 1) / spw) * spw; };
+    if (m.np > nslot || m.np > 64) return false;       // pairs_compacted() == false; one-level prefix (none runs on this tile)
+    if (wave_up(m.np) + m.nb > nslot) return false;    // integrate_bodies beside the pairs: pose_in_off == L.xiq.off (overlap)
+    if (wave_up(m.nb) + m.nb > nslot) return false;    // body_lane_split() != 0 (lane_split is the kernel's own compile-time fact)
+    return true;
+}
+
+XpbdRoute plan_xpbd_rollout(const KArgs& a, const nt_collide_params* cp, XpbdCfg& c) {
+    const nt_model& m = a.m;
+    const bool rest = xpbd_keeps_prestep_state(a.p);
     const int epb = pick_epb(m, cp ? cp->envs_per_block : 0, rest);
     if (!epb) return XpbdRoute::none;
     const bool cvx = m.np_analytic < m.np;
     if (m.contact_scratch_in_hbm) {
-        c = {1, big_wide_fits(m, rest) ? NT_BIG_SCENE_LANES_WIDE : NT_BIG_SCENE_LANES, 1, 0, 0};
+        c = {1, big_wide_fits(m, rest) ? NT_BIG_SCENE_LANES_WIDE : NT_BIG_SCENE_LANES, 1, 0, 0, 0};
         return XpbdRoute::tile;
     }
     // the tuned shapes: an override for this kind of model, else the uniform-parameter tiles when the parameters allow
     XpbdCfg o;
-    if (xpbd_cfg_override(o) && (o.cvx != 0) == cvx) {
+    int spec_request = -1;  // (NT_XPBD_CFG's sixth field: 0 generic, 1 specialised or refused; -1: NT_XPBD_SPEC_DEFAULT)
+    if (xpbd_cfg_override(o, spec_request) && (o.cvx != 0) == cvx) {
         c = o;
-        return (o.uni && (!m.params_uniform || rest)) || !epb_fits(m, o.epb, rest, o.uni != 0) ? XpbdRoute::refused : XpbdRoute::shape;
+        if ((o.uni & ~1) || (o.uni && (!m.params_uniform || rest)) || !epb_fits(m, o.epb, rest, o.uni != 0)) return XpbdRoute::refused;
+        c.spec = (spec_request < 0 ? NT_XPBD_SPEC_DEFAULT : spec_request != 0) && xpbd_spec_tile_fits(a, c) ? 1 : 0;
+        return spec_request > 0 && !c.spec ? XpbdRoute::refused : XpbdRoute::shape;
     }
     if (cvx ? (cp == nullptr || cp->envs_per_block == 0) && pick_cvx_uni_shape(m, rest, o) : pick_uni_shape(m, rest, cp, o)) {
         c = o;
+        c.spec = NT_XPBD_SPEC_DEFAULT && xpbd_spec_tile_fits(a, c) ? 1 : 0;
         return XpbdRoute::shape;
     }
     const int e = collide_tile_epb(cvx, epb);
-    c = {e, max_threads_for(e), 1, 0, 0};
+    c = {e, max_threads_for(e), 1, 0, 0, 0};
     return XpbdRoute::tile;
 }
 
@@ -492,20 +550,13 @@ nt_status nt_xpbd_step(const nt_model* m, const nt_xpbd_params* p, nt_state* s_i
 nt_status nt_xpbd_rollout(const nt_model* m, const nt_xpbd_params* p, const nt_collide_params* cp, nt_state* s0, nt_state* s1,
                           const nt_control* ctrl, nt_contacts* c, float dt, int32_t substeps, void* stream) {
     if (!model_ok(m) || !p || !s0 || !s1 || !ctrl || !c || substeps < 1) return NT_ERR_INVALID_ARG;
-    KArgs a = {};
-    a.m = *m;
+    KArgs a = xpbd_rollout_args(*m, *p, dt, substeps);
     a.s_in = *s0;
     a.s_out = *s1;
     a.c = *ctrl;
     a.ct = *c;
-    a.has_contacts = m->np > 0 ? 1 : 0;
-    a.p = *p;
-    a.angular_damping = p->angular_damping;
-    a.dt = dt;
-    a.substeps = substeps;
-    a.tile_opts = NT_TILE_POSE_SNAPSHOT | NT_TILE_LDS_RECORDS;  // (request; launch() grants what the tile has room for)
     XpbdCfg shape;
-    const XpbdRoute route = plan_xpbd_rollout(*m, xpbd_keeps_prestep_state(*p), cp, shape);
+    const XpbdRoute route = plan_xpbd_rollout(a, cp, shape);
     if (route == XpbdRoute::none || route == XpbdRoute::refused) return NT_ERR_UNSUPPORTED;
     if (route == XpbdRoute::shape) return launch_xpbd_rollout_shape(a, shape, (hipStream_t)stream);
 #ifdef NT_DEV_FAST
@@ -525,10 +576,13 @@ nt_status nt_xpbd_rollout(const nt_model* m, const nt_xpbd_params* p, const nt_c
 
 nt_status nt_xpbd_rollout_shape(const nt_model* m, const nt_xpbd_params* p, const nt_collide_params* cp, int32_t out[5]) {
     if (!model_ok(m) || !p || !out) return NT_ERR_INVALID_ARG;
-    XpbdCfg c;
-    if (plan_xpbd_rollout(*m, xpbd_keeps_prestep_state(*p), cp, c) == XpbdRoute::none) return NT_ERR_UNSUPPORTED;
+    XpbdCfg c = {};
+    // (the launch's own plan on the launch's own arguments; the Contacts are not known here: a launch whose Contacts carry rows of the
+    // SDF legs runs the generic instance whatever bit 4 says)
+    const XpbdRoute route = plan_xpbd_rollout(xpbd_rollout_args(*m, *p, 0.0f, 1), cp, c);
+    if (route == XpbdRoute::none) return NT_ERR_UNSUPPORTED;
     out[0] = c.epb; out[1] = c.threads; out[2] = c.minw; out[3] = c.uni;
-    out[4] = (m->np_analytic < m->np ? 1 : 0) | (m->contact_scratch_in_hbm ? 2 : 0);
+    out[4] = (m->np_analytic < m->np ? 1 : 0) | (m->contact_scratch_in_hbm ? 2 : 0) | (route == XpbdRoute::shape && c.spec ? 4 : 0);
     return NT_OK;
 }
 

@@ -192,6 +192,7 @@ NT_DI void integrate_item(const Ctx<EPB>& c, const int b) {
 NT_DI bool xpbd_applies_follow(const KArgs& a) { return a.p.iterations > 0 && (a.has_contacts != 0 || a.m.nj > 0); }
 template <int EPB>
 NT_DI int body_lane_split(const Ctx<EPB>& c) {  // S0 if the linear lanes fit behind the angular ones, else 0 (one lane per body)
+    if constexpr (Ctx<EPB>::SPEC) return c.R.B0;  // (the launch code verified that the lanes fit; callers know it is not 0)
     const int spw = 64 / Ctx<EPB>::N > 0 ? 64 / Ctx<EPB>::N : 1;
     const int S0 = ((c.a.m.nb + spw - 1) / spw) * spw;
     return c.lane_split && S0 + c.a.m.nb <= c.nslot ? S0 : 0;
@@ -254,7 +255,7 @@ template <int EPB>
 NT_DI void phase_xpbd_integrate(const Ctx<EPB>& c, const bool need_p) {
     if (!c.valid) return;
     const int nb = c.a.m.nb, S0 = need_p ? 0 : body_lane_split(c);
-    if (S0) {
+    if ((Ctx<EPB>::SPEC && !need_p) || S0) {
         if (c.slot < nb) xpbd_integrate_item(c, c.slot, false, true, false);
         else if (c.slot >= S0 && c.slot < S0 + nb) xpbd_integrate_item(c, c.slot - S0, true, false, false);
     } else {
@@ -857,7 +858,7 @@ template <int EPB, bool FROM_CONTACTS, class CW = CwLds, bool FUSED = false, boo
 NT_DI void phase_apply(const Ctx<EPB>& c, const bool last) {
     if (!c.valid) return;
     const int nb = c.a.m.nb, S0 = body_lane_split(c);
-    if (S0) {
+    if (Ctx<EPB>::SPEC || S0) {
         if (c.slot < nb) apply_item<EPB, FROM_CONTACTS, CW, FUSED, ROWS>(c, c.slot, false, true, last);
         else if (c.slot >= S0 && c.slot < S0 + nb) apply_item<EPB, FROM_CONTACTS, CW, FUSED, ROWS>(c, c.slot - S0, true, false, last);
     } else {
@@ -1500,7 +1501,7 @@ NT_DI void phase_joints(const Ctx<EPB>& c) {
     // holds 64 / EPB slots): no wavefront then mixes the two code paths, so the phase costs max(linear, angular)
     // instead of their sum in the wave that used to straddle the boundary
     const int spw = 64 / Ctx<EPB>::N > 0 ? 64 / Ctx<EPB>::N : 1;
-    const int A0 = ((nj + spw - 1) / spw) * spw;
+    const int A0 = Ctx<EPB>::SPEC ? c.R.A0 : ((nj + spw - 1) / spw) * spw;
     NT_SKIP_DECL(c.a);  // (measurement builds: 32 skips the linear-row lanes, 64 the angular-row lanes)
     for (int i = c.slot; i < A0 + nj; i += c.nslot) {
         if (i < nj) { if (!NT_SKIP(32)) joint_linear_item(c, i); }
@@ -1515,8 +1516,11 @@ template <int EPB, bool FUSED, class CW = CwLds, bool PROLOGUE_DONE = false, boo
 NT_DI void do_xpbd_step(const Ctx<EPB>& c, bool forces_are_zero) {
     const nt_model& m = c.a.m;
     NT_SKIP_DECL(c.a);
-    const bool restitution = c.a.p.enable_restitution && c.a.has_contacts;
-    const bool vel_from_delta = c.a.p.compute_body_velocity_from_position_delta != 0;
+    // NT_SPEC (fused rollout instance): the launch code verified these solver options and model features
+    constexpr bool SPEC = Ctx<EPB>::SPEC;
+    const bool restitution = !SPEC && c.a.p.enable_restitution && c.a.has_contacts;
+    const bool vel_from_delta = !SPEC && c.a.p.compute_body_velocity_from_position_delta != 0;
+    const bool has_contacts = SPEC || c.a.has_contacts != 0, has_joints = SPEC || m.nj > 0;
     if (!PROLOGUE_DONE && (restitution || vel_from_delta) && c.valid)  // body_q_init / body_qd_init: the state the step starts from
         for (int r = c.slot; r < 14 * m.nb; r += c.nslot) c.lds[(c.L.xiq.off + r) * Ctx<EPB>::N + c.e] = c.lds[(c.L.bq.off + r) * Ctx<EPB>::N + c.e];
     const bool rep_joints = !FUSED && c.a.rep.joint_impulse != nullptr;
@@ -1531,9 +1535,10 @@ NT_DI void do_xpbd_step(const Ctx<EPB>& c, bool forces_are_zero) {
         NT_TICK(4);
     }
     const int iterations = c.a.p.iterations;
+    if constexpr (SPEC) NT_ASSUME(iterations > 0);
     for (int it = 0; it < iterations; ++it) {
         const bool last_it = it == iterations - 1;
-        if (c.a.has_contacts) {
+        if (has_contacts) {
             if (!NT_SKIP(4)) phase_contacts<EPB, FUSED, CW, ROWS>(c);
             __syncthreads();
             NT_TICK(5);
@@ -1541,11 +1546,11 @@ NT_DI void do_xpbd_step(const Ctx<EPB>& c, bool forces_are_zero) {
                 report_contact_iteration<EPB, CW>(c, it == 0);
                 if constexpr (!FUSED) report_flat_rows_iteration<EPB, CW>(c, it == 0);
             }
-            if (!NT_SKIP(16)) phase_apply<EPB, true, CW, FUSED, ROWS>(c, last_it && m.nj <= 0);
+            if (!NT_SKIP(16)) phase_apply<EPB, true, CW, FUSED, ROWS>(c, last_it && !has_joints);
             __syncthreads();
             NT_TICK(6);
         }
-        if (m.nj > 0) {
+        if (has_joints) {
             if (!NT_SKIP(8)) phase_joints(c);
             __syncthreads();
             NT_TICK(7);

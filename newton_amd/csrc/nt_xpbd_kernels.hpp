@@ -55,20 +55,25 @@ NT_DI void do_fused_substep(const Ctx<EPB>& c, const fused::Ctx<EPB>& cf, bool l
     const nt_model& m = c.a.m;
     NT_SKIP_DECL(c.a);
     const int spw = 64 / Ctx<EPB>::N > 0 ? 64 / Ctx<EPB>::N : 1;  // slots per wave
-    const bool restitution = (c.a.p.enable_restitution && c.a.has_contacts) || c.a.p.compute_body_velocity_from_position_delta != 0;
+    // NT_SPEC: what the launch code verified (xpbd_spec_tile_fits) is a constant here -- no pre-step state kept, pairs in one
+    // uncompacted pass, integrate_bodies beside them, an apply phase follows; the slot ranges come from the context
+    constexpr bool SPEC = Ctx<EPB>::SPEC;
+    const bool restitution =
+        !SPEC && ((c.a.p.enable_restitution && c.a.has_contacts) || c.a.p.compute_body_velocity_from_position_delta != 0);
     // -- interval 1: shapes (slots [0, ns)) || joint forces (slots [S0, S0 + nj), S0 on a wave boundary) + body_f_tmp = 0
     const bool compact = pairs_compacted(c);
     // integrate_bodies beside the pair phase (its 13 lanes on the waves the 13 pair lanes leave idle; the pair phase is the longer of
     // the two): the contact writer then converts into the snapshot of the incoming poses (c.pose_in_off) taken in interval 1
-    const int I0 = ((m.np + spw - 1) / spw) * spw;
-    const bool overlap = c.pose_in_off != c.L.bq.off;
+    const int I0 = SPEC ? c.R.I0 : ((m.np + spw - 1) / spw) * spw;
+    const bool overlap = SPEC || c.pose_in_off != c.L.bq.off;
+    const bool need_p = !SPEC && !fused::xpbd_applies_follow(c.a);  // integrate_bodies rebuilds the body origins itself
     if (c.valid) {
         if (compact && c.slot == 0) *reinterpret_cast<int*>(&c.l(c.L.hc, 0, 1, 0)) = 0;
         if (c.lds_records && c.slot == 0) *reinterpret_cast<int*>(&c.l(c.L.lc, 0, 1, 0)) = 0;
         if (restitution || overlap)
             for (int r = c.slot; r < (restitution ? 14 : 7) * m.nb; r += c.nslot) c.lds[(c.L.xiq.off + r) * Ctx<EPB>::N + c.e] = c.lds[(c.L.bq.off + r) * Ctx<EPB>::N + c.e];
         if (!NT_SKIP(2)) fused::seed_body_forces(cf, true);
-        const int S0 = ((m.ns + spw - 1) / spw) * spw;
+        const int S0 = SPEC ? c.R.S0 : ((m.ns + spw - 1) / spw) * spw;
         for (int i = c.slot; i < S0 + m.nj; i += c.nslot) {
             if (i < m.ns) {
                 if (!NT_SKIP(1)) shape_item(c, i);
@@ -86,7 +91,7 @@ NT_DI void do_fused_substep(const Ctx<EPB>& c, const fused::Ctx<EPB>& cf, bool l
             __syncthreads();
             phase_pair_narrow_staged<EPB, CVX>(c);
         } else if (overlap && c.slot >= I0) {
-            if (c.valid && c.slot < I0 + m.nb && !NT_SKIP(2)) fused::xpbd_integrate_item(cf, c.slot - I0, true, true, !fused::xpbd_applies_follow(c.a));
+            if (c.valid && c.slot < I0 + m.nb && !NT_SKIP(2)) fused::xpbd_integrate_item(cf, c.slot - I0, true, true, need_p);
         } else {
             phase_pair_eval<EPB, CVX>(c);
         }
@@ -126,7 +131,7 @@ NT_DI void do_fused_substep(const Ctx<EPB>& c, const fused::Ctx<EPB>& cf, bool l
     NT_TICK(3);
     // -- interval 4: integrate_bodies (unless it ran beside the pairs)
     if (!overlap) {
-        if (!NT_SKIP(2)) fused::phase_xpbd_integrate(cf, !fused::xpbd_applies_follow(c.a));
+        if (!NT_SKIP(2)) fused::phase_xpbd_integrate(cf, need_p);
         __syncthreads();
     }
     NT_TICK(4);
@@ -216,7 +221,12 @@ __global__ void __launch_bounds__(THREADS, MINW) xpbd_rollout_kernel(KArgs a) {
     Ctx<EPB> c(a, lds, -1, BIG);
     if constexpr (CVX || BIG) c.lds_records = false;  // (granted to analytic-only staged tiles alone: folds the LDS-record code away here)
     c.lane_split = !(CVX || Ctx<EPB>::N >= 32);  // (a compile-time fact per kernel; 32-environment tiles have no idle waves to split onto)
-    if constexpr (!BIG) {  // (the layout holds the snapshot rows, the pairs fit one pass and the integrate lanes fit behind them)
+    if constexpr (Ctx<EPB>::SPEC) {  // (granted tile extras and model features the launch code verified: xpbd_spec_tile_fits)
+        static_assert(!CVX && !BIG && Ctx<EPB>::UNI && Ctx<EPB>::N == 16, "NT_SPEC: the analytic uniform-parameter tile of 16 only");
+        c.lds_records = true;
+        c.L.has_lt = 1;
+        c.pose_in_off = c.L.xiq.off;
+    } else if constexpr (!BIG) {  // (the layout holds the snapshot rows, the pairs fit one pass and the integrate lanes fit behind them)
         constexpr int spw = 64 / Ctx<EPB>::N > 0 ? 64 / Ctx<EPB>::N : 1;
         if ((a.tile_opts & NT_TILE_POSE_SNAPSHOT) && a.m.np <= a.nslot && ((a.m.np + spw - 1) / spw) * spw + a.m.nb <= a.nslot)
             c.pose_in_off = c.L.xiq.off;
