@@ -78,8 +78,18 @@ typedef struct {
     int32_t params_uniform; /* 1: body_param / joint_param / dof_param / shape_param hold the same values in every environment
                             (replicated worlds, newton.ModelBuilder.replicate without per-world randomisation).  The XPBD rollout
                             then keeps ONE block-shared copy per workgroup in LDS; 0 is always valid */
+    int32_t tile_image_words; /* 0: no tile image, the kernels stage the block-shared region of their tile from the tables below
+                            (always valid: what a descriptor filled in by hand carries).  > 0, set by nt_model_create /
+                            nt_model_refresh_params only: body_flags points at the TILE IMAGE, this many words long -- what is the
+                            same for every workgroup and every launch (the 23 topology tables, body_flags first, gshape_param,
+                            joint_inc, pair_desc and, while params_uniform holds, the one parameter copy of a uniform-parameter
+                            tile) packed word for word as the kernels lay it out in LDS, so that a
+                            workgroup copies it with one batch of 16-byte loads.  The image is 16-byte aligned and readable up to
+                            the count rounded up to a multiple of 4.  Derived data: a host that edits a table or a size of this
+                            descriptor by hand sets 0.  (The field fills what was alignment padding: the struct's size and every
+                            other offset are unchanged.) */
     /* topology, int32, env-uniform */
-    const int32_t* body_flags;          /* [nb]   BodyFlags */
+    const int32_t* body_flags;          /* [nb]   BodyFlags (tile_image_words > 0: the first table of the tile image) */
     const int32_t* joint_type;          /* [nj]   JointType */
     const int32_t* joint_enabled;       /* [nj] */
     const int32_t* joint_parent;        /* [nj]   env-local body index or -1 */

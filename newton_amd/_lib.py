@@ -35,6 +35,7 @@ class nt_model(C.Structure):
         ("np_analytic", C.c_int32), ("na", C.c_int32), ("max_art_dofs", C.c_int32), ("shape_local0", C.c_int32),
         ("contact_scratch_in_hbm", C.c_int32),
         ("params_uniform", C.c_int32),
+        ("tile_image_words", C.c_int32),  # (where the C struct had alignment padding)
         ("body_flags", C.c_void_p), ("joint_type", C.c_void_p), ("joint_enabled", C.c_void_p),
         ("joint_parent", C.c_void_p), ("joint_child", C.c_void_p), ("joint_q_start", C.c_void_p),
         ("joint_qd_start", C.c_void_p), ("joint_tq_start", C.c_void_p), ("joint_lin_count", C.c_void_p),

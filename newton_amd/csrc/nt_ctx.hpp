@@ -49,7 +49,8 @@ struct Ctx {
     struct Ranges { int B0, S0, I0, A0; } R;  // linear body lanes, joint-force lanes, integrate lanes, angular joint lanes
 
     // rows: float rows per env in front of the block-shared topology ints (-1: the XPBD / collide layout)
-    NT_DI Ctx(const KArgs& a_, float* lds_, int rows = -1, const bool big_ = false) : a(a_), lds(lds_), big(big_) {
+    // defer_image: the kernel calls load_tile next (see issue_image)
+    NT_DI Ctx(const KArgs& a_, float* lds_, int rows = -1, const bool big_ = false, const bool defer_image = false) : a(a_), lds(lds_), big(big_) {
         // (rows >= 0: another solver's layout, no live list; the pair-heavy tile sizes its per-lane polygon scratch by the workgroup
         // the launch code chose: 256 lanes, or NT_BIG_SCENE_LANES_WIDE when they fit)
         L = make_layout(a.m, big_, xpbd_keeps_prestep_state(a.p), UNI, rows < 0, a.tile_opts,
@@ -68,13 +69,114 @@ struct Ctx {
         tslot = slot;
         const nt_model& m = a.m;
         R = {wave_up(m.nb), wave_up(m.ns), wave_up(m.np), wave_up(m.nj)};
-        int* ti = reinterpret_cast<int*>(lds + (size_t)rows * N);
+        ti = reinterpret_cast<int*>(lds + (size_t)rows * N);
+        up = reinterpret_cast<float*>(ti + topo_ints(m));
+        gworld_ready = false;
+        lane_split = true;
+        has_image = IMAGE && m.tile_image_words >= topo_ints(m);  // (the image then starts at m.body_flags)
+        img.pending = img.params = false;
+        if constexpr (IMAGE) {
+            if (has_image) issue_image(defer_image);
+            else stage_topology();
+        } else {
+            stage_topology();
+        }
+    }
+    // The tiles of 32 and 64 environments keep the table-by-table staging: with the image code in them the substep loop of the
+    // 32-wide rollout instance was scheduled 4 % slower (8 192 / 65 536 quadrupeds: 249.1 -> 239.5 M env-steps/s with NT_TILE_IMAGE=0,
+    // 246.7 with the image; profiles/tile_image_ab.txt), more than the shorter prologue gives back at two workgroups per CU and more.
+    static constexpr bool IMAGE = N < 32;
+    // nt_model.tile_image_words set (the image starts at m.body_flags): the block-shared region is one copy.  Every lane issues its 16-byte loads of the image
+    // (workgroup-strided, the first NT_IMAGE_TRIPS of them in flight together) before the first LDS write; T.* and `up` are plain
+    // offsets.  The gworld range and the pair-heavy tile's hit list stay unwritten (stage_global_world / the pair-heavy kernels fill
+    // them).  defer: the kernel calls load_tile next and leaves `up` where it is (the collide / XPBD kernels) -- the stores wait for
+    // commit_image(), which load_tile calls behind ITS loads, so that image, state and controls are one memory round trip, and the
+    // image's parameter block is taken.  Kernels of the other solvers put tables of their own behind the topology and move `up`
+    // behind those: they take the topology part only and load the parameter copy as without an image.
+    // 4-byte LDS stores: the region starts behind rows * N floats, 16-byte aligned for some N only.
+    static constexpr int NT_IMAGE_TRIPS = 2;
+    struct Image {
+        TileImageQuad v[NT_IMAGE_TRIPS];
+        int total;           // words to copy: the topology [+ the parameter block of a uniform-parameter tile]
+        int g0, g1, h0, h1;  // the two ranges left unwritten
+        bool pending;        // loads issued, stores outstanding
+        bool params;         // the image fills `up`: load_uniform_params has nothing to do
+    };
+    mutable Image img;
+    int* ti;
+    bool has_image;
+    NT_DI void issue_image(const bool defer) {
+        const nt_model& m = a.m;
+        const TopoTables tt = topo_tables(m);
+        const int** const dsts[NT_TOPO_TABLES] = {
+            &T.body_flags, &T.joint_type, &T.joint_enabled, &T.joint_parent, &T.joint_child, &T.joint_q_start, &T.joint_qd_start,
+            &T.joint_tq_start, &T.joint_lin_count, &T.joint_ang_count, &T.shape_body, &T.shape_type, &T.shape_flags, &T.shape_group,
+            &T.pair_a, &T.pair_b, &T.body_joint_start, &T.body_joint_list, &T.body_pair_start, &T.body_pair_list, &T.shape_mesh_start,
+            &T.shape_mesh_count, &T.gshape_id};
+        int o = 0;
+#pragma unroll
+        for (int k = 0; k < NT_TOPO_TABLES; ++k) {
+            *dsts[k] = ti + o;
+            o += tt.len[k];
+        }
+        T.gshape = reinterpret_cast<float*>(ti + o);
+        o += NT_SHAPE_PARAM_FLOATS * m.ng;
+        T.gworld = reinterpret_cast<float*>(ti + o);
+        img.g0 = o;
+        o += 13 * m.ng;
+        img.g1 = o;
+        T.joint_inc = ti + o;
+        o += 2 * m.nj;
+        T.hit_count = ti + o;
+        T.hit_list = ti + o + 1;
+        T.pair_desc = ti + o;  // (the two tables exclude each other)
+        const int topo = topo_ints(m);
+        img.h0 = m.contact_scratch_in_hbm ? o : topo;
+        img.h1 = topo;
+        img.total = topo;
+        if constexpr (UNI) {
+            if (defer && m.tile_image_words >= topo + L.uni_floats) {
+                img.total = topo + L.uni_floats;
+                img.params = true;
+            }
+        }
+        const TileImageQuad* src = reinterpret_cast<const TileImageQuad*>(m.body_flags);
+        const int n4 = (img.total + 3) / 4;  // (the image is readable up to a multiple of four words)
+#pragma unroll
+        for (int k = 0; k < NT_IMAGE_TRIPS; ++k) {
+            const int i4 = (int)threadIdx.x + k * (int)blockDim.x;
+            img.v[k] = i4 < n4 ? src[i4] : TileImageQuad{{0, 0, 0, 0}};
+        }
+        img.pending = true;
+        if (!defer) commit_image();
+    }
+    NT_DI void image_store(const int i4, const TileImageQuad& v) const {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int w = 4 * i4 + k;
+            if (w < img.total && !(w >= img.g0 && w < img.g1) && !(w >= img.h0 && w < img.h1)) ti[w] = v.w[k];
+        }
+    }
+    NT_DI void commit_image() const {
+        if (!img.pending) return;
+        img.pending = false;
+        const int n4 = (img.total + 3) / 4;
+#pragma unroll
+        for (int k = 0; k < NT_IMAGE_TRIPS; ++k) {
+            const int i4 = (int)threadIdx.x + k * (int)blockDim.x;
+            if (i4 < n4) image_store(i4, img.v[k]);
+        }
+        const TileImageQuad* src = reinterpret_cast<const TileImageQuad*>(a.m.body_flags);
+        for (int i4 = (int)threadIdx.x + NT_IMAGE_TRIPS * (int)blockDim.x; i4 < n4; i4 += blockDim.x) image_store(i4, src[i4]);
+    }
+    // no image (nt_model.tile_image_words == 0): the region is staged table by table from the descriptor's own tables
+    NT_DI void stage_topology() {
+        const nt_model& m = a.m;
         int o = 0;
         // The 24 env-uniform tables are fetched FIRST -- every thread one element of each, all loads in flight together -- and
         // written to LDS afterwards.  (One copy loop per table compiles to load / s_waitcnt vmcnt(0) / ds_write per table: 24
         // serialised memory round trips, ~25 us per launch -- most of what a per-call collide / step kernel took, 8 % of a
         // 10-substep rollout launch.)  Tables longer than the workgroup finish in a tail loop.
-        constexpr int NT_TOPO_TABLES = 23;
         const int32_t* const srcs[NT_TOPO_TABLES] = {
             m.body_flags, m.joint_type, m.joint_enabled, m.joint_parent, m.joint_child, m.joint_q_start, m.joint_qd_start, m.joint_tq_start,
             m.joint_lin_count, m.joint_ang_count, m.shape_body, m.shape_type, m.shape_flags, m.shape_group, m.pair_a, m.pair_b,
@@ -109,8 +211,6 @@ struct Ctx {
         }
         T.gworld = reinterpret_cast<float*>(ti + o);
         o += 13 * m.ng;
-        gworld_ready = false;
-        lane_split = true;
         T.joint_inc = ti + o;  // (filled by stage_joint_inc, one barrier after the tables above are published)
         o += 2 * m.nj;
         T.hit_count = ti + o;
@@ -125,14 +225,16 @@ struct Ctx {
                 ti[o + 4 * i + 3] = (m.shape_body[sb] & 0x3fffffff) | (swapped << 30);
             }
         }
-        up = reinterpret_cast<float*>(ti + topo_ints(m));
     }
     // the same lane seen from the other arithmetic namespace (ieee::Ctx <-> fused::Ctx): no staging, every member copied
     template <class OtherCtx>
     NT_DI explicit Ctx(const OtherCtx& o, int /*tag*/)
         : a(o.a), T(o.T), lds(o.lds), up(o.up), L(o.L), e(o.e), slot(o.slot), env(o.env), nslot(o.nslot), tslot(o.tslot),
           pose_in_off(o.pose_in_off), lane_split(o.lane_split), gworld_ready(o.gworld_ready), lds_records(o.lds_records), hbm_out(o.hbm_out), aos_records(o.aos_records), big(o.big),
-          ES(o.ES), valid(o.valid), R{o.R.B0, o.R.S0, o.R.I0, o.R.A0} {}
+          ES(o.ES), valid(o.valid), R{o.R.B0, o.R.S0, o.R.I0, o.R.A0}, ti(o.ti), has_image(o.has_image) {
+        img.pending = false;  // (the staging belongs to the lane's first context)
+        img.params = o.img.params;
+    }
     static NT_DI int wave_up(int n) { return ((n + SPW - 1) / SPW) * SPW; }  // n rounded up to whole waves of slots
     // LDS element (comp, s) of a slot-major field.  `n` (the slot count of the [comp][n] HBM twin) is not needed here; the
     // argument stays so that every access reads like its global-memory counterpart g(comp, n, s)
@@ -209,6 +311,7 @@ struct Ctx {
     // inverse of body_joint_list: position of code (j << 1 | side) in the list, -1 for the world side of a root joint.  Reads the
     // block-shared copy of the list, i.e. runs one barrier after the constructor; the XPBD joint phases are barriers later still
     NT_DI void stage_joint_inc() const {
+        if (has_image) return;  // (the image carries the table)
         const int nlist = a.m.nj > 0 ? T.body_joint_start[a.m.nb] : 0;
         int* inv = const_cast<int*>(T.joint_inc);
         for (int i = threadIdx.x; i < 2 * a.m.nj; i += blockDim.x) {
@@ -384,9 +487,10 @@ NT_DI void stage_rows_rest(const Ctx<EPB>& c, Fld<NC> f, const float* src, int n
 }
 
 // the block-shared parameter copy of a uniform-parameter tile: one copy per workgroup, read from the tile's first environment (the
-// host vouches that all columns are equal)
+// host vouches that all columns are equal).  Only where the tile image does not hold the copy
 template <int EPB>
 NT_DI void load_uniform_params(const Ctx<EPB>& c) {
+    if (c.img.params) return;  // (the tile image carried the copy: nt_model.tile_image_words)
     const nt_model& m = c.a.m;
     const int nb = m.nb;
     auto body_value = [&](int comp, int b, size_t col) {
@@ -457,7 +561,10 @@ NT_DI void load_tile(const Ctx<EPB>& c, const nt_state* state, bool with_control
     const int nb = m.nb;
     constexpr bool UNI = Ctx<EPB>::UNI;
     if constexpr (UNI) load_uniform_params(c);  // (the block-shared parameter copy: workgroup-strided loops)
-    if (!c.valid) return;
+    if (!c.valid) {
+        c.commit_image();
+        return;
+    }
     float vq[7], vqd[6], vbp[NT_BODY_PARAM_FLOATS], vjp[NT_JOINT_PARAM_FLOATS], vdp[NT_DOF_PARAM_FLOATS], vsp[NT_SHAPE_PARAM_FLOATS];
     float vg[3] = {0.0f, 0.0f, 0.0f}, vcf = 0.0f, vctq = 0.0f, vctqd = 0.0f;
     int flags = 0;
@@ -480,7 +587,8 @@ NT_DI void load_tile(const Ctx<EPB>& c, const nt_state* state, bool with_control
         if (c.slot < m.nd) { vcf = c.a.c.joint_f[c.g(0, m.nd, c.slot)]; vctqd = c.a.c.joint_target_qd[c.g(0, m.nd, c.slot)]; }
         if (c.slot < m.ntq) vctq = c.a.c.joint_target_q[c.g(0, m.ntq, c.slot)];
     }
-    // ---- writes
+    // ---- writes (first a deferred tile image: its loads left before the ones above)
+    c.commit_image();
     if (state) {
         first_store(c, c.L.bq, nb, vq);
         first_store(c, c.L.bqd, nb, vqd);

@@ -229,6 +229,28 @@ __host__ __device__ inline int topo_ints(const nt_model& m) {
     return m.nb + 9 * m.nj + 6 * (m.ns + m.ng) + 2 * m.np + 2 * (m.nb + 1) + 2 * m.nj + 2 * m.np + m.ng +
            NT_SHAPE_PARAM_FLOATS * m.ng + 13 * m.ng + 2 * m.nj + (m.contact_scratch_in_hbm ? 1 + m.np : 4 * m.np);
 }
+// The block-shared region in the order Ctx lays it out: the tables of Topo up to gshape_id (sources and lengths below), gshape
+// [NT_SHAPE_PARAM_FLOATS ng], gworld [13 ng], joint_inc [2 nj], then pair_desc [4 np] or (pair-heavy tile) hit_count + hit_list
+// [1 + np] -- topo_ints(m) words; the parameter copy of a uniform-parameter tile follows.  The tile image (nt_model.tile_image_words) is this region packed
+// on the host (nt_model_build.hip), which walks the same list: the order is written down here and nowhere else.
+constexpr int NT_TOPO_TABLES = 23;
+struct TopoTables {
+    const int32_t* src[NT_TOPO_TABLES];
+    int len[NT_TOPO_TABLES];
+};
+__host__ __device__ inline TopoTables topo_tables(const nt_model& m) {
+    const int nsg = m.ns + m.ng;
+    return TopoTables{
+        {m.body_flags, m.joint_type, m.joint_enabled, m.joint_parent, m.joint_child, m.joint_q_start, m.joint_qd_start, m.joint_tq_start,
+         m.joint_lin_count, m.joint_ang_count, m.shape_body, m.shape_type, m.shape_flags, m.shape_group, m.pair_a, m.pair_b,
+         m.body_joint_start, m.body_joint_list, m.body_pair_start, m.body_pair_list, m.shape_mesh_start, m.shape_mesh_count, m.gshape_id},
+        {m.nb, m.nj, m.nj, m.nj, m.nj, m.nj, m.nj, m.nj, m.nj, m.nj, nsg, nsg, nsg, nsg, m.np, m.np,
+         m.nb + 1, 2 * m.nj /* padded by the host */, m.nb + 1, 2 * m.np /* padded */, nsg, nsg, m.ng}};
+}
+// 16 bytes of the tile image (one global_load_dwordx4 per lane)
+struct alignas(16) TileImageQuad {
+    int32_t w[4];
+};
 
 // ------------------------------------------------------------------------------------------------
 // optional per-phase cycle accounting (-DNT_PHASE_TIMING, tools/phase_timing.py): workgroup 0 / thread 0 accumulates the

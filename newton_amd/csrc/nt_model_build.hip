@@ -6,6 +6,7 @@
 // and the env-major SoA parameter tables, and places them in HIP device memory (or host memory, for inspection and tests).
 // It is the C restatement of the Python host logic in newton_amd/model.py (EnvTemplate, pack_param_arrays, params_uniform,
 // choose_contact_scratch); tests/test_model_build.py holds the two against each other table by table.
+// On top of the tables it packs the tile image (nt_model.tile_image_words, found at body_flags): the block-shared region of the kernels' LDS tile, word for word (write_tile_image).
 // Host code only: no kernels in this unit.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -20,6 +21,8 @@
 
 namespace {
 
+#include "nt_layout.hpp"  // (the tile's layout: make_layout, topo_ints, topo_tables -- the image below restates none of it)
+
 thread_local std::string g_error;
 
 struct Fail {
@@ -31,7 +34,6 @@ struct Fail {
 
 enum { GEO_PLANE = 1, GEO_HFIELD = 2, GEO_SPHERE = 3, GEO_CAPSULE = 4, GEO_ELLIPSOID = 5, GEO_CYLINDER = 6, GEO_BOX = 7, GEO_MESH = 8, GEO_CONE = 9, GEO_CONVEX_MESH = 10 };
 constexpr int SHAPE_HYDROELASTIC = 1 << 4;  // ShapeFlags.HYDROELASTIC
-constexpr int BODY_KINEMATIC = 2;
 
 bool analytic_pair(int ta, int tb) {  // narrow_phase.py:642-655: pairs with a closed-form primitive routine
     if (ta > tb) std::swap(ta, tb);
@@ -53,13 +55,21 @@ struct nt_model_handle {
     std::vector<std::vector<int32_t>> itab;
     std::vector<std::vector<float>> ftab;
     std::vector<void*> dev;
+    std::vector<const void*> iaddr;  // what put() answered for itab[k]: the address the descriptor carries
     std::vector<int64_t> pair_order;
     std::vector<int32_t> sdf_pairs;  // pairs that leave the tiles: [n][2] template shape ids
     std::vector<uint8_t> sdf_kind, sdf_has_edges;
 
     const int32_t* put(const std::vector<int32_t>& v) {
         itab.push_back(v.empty() ? std::vector<int32_t>(1, 0) : v);
-        return (const int32_t*)place(itab.back().data(), itab.back().size() * 4);
+        iaddr.push_back(place(itab.back().data(), itab.back().size() * 4));
+        return (const int32_t*)iaddr.back();
+    }
+    // the host copy of an int table of the descriptor
+    std::vector<int32_t>& host_of(const int32_t* p) {
+        for (size_t k = 0; k < iaddr.size(); ++k)
+            if (iaddr[k] == p) return itab[k];
+        throw Fail{NT_ERR_INVALID_ARG, "not a table of this handle"};
     }
     const float* put(const std::vector<float>& v) {
         ftab.push_back(v.empty() ? std::vector<float>(1, 0.0f) : v);
@@ -94,6 +104,8 @@ struct Params {
     std::vector<float> body, gravity, joint, dof, shape, gshape;
     int uniform;
 };
+
+std::vector<int32_t> pack_tile_image(nt_model_handle& h, const Params& P, int& words);
 
 // pack_param_arrays + params_uniform (newton_amd/model.py)
 Params pack_params(const nt_newton_model& s, const nt_model& d, const std::vector<int32_t>& gshape_id) {
@@ -453,6 +465,79 @@ void build(const nt_newton_model& s, nt_model_handle& h) {
         d.contact_scratch_in_hbm = 1;
         if (nt_pick_envs_per_block(&d, 0) == 0) d.contact_scratch_in_hbm = 0;
     }
+    int words = 0;
+    const std::vector<int32_t> image = pack_tile_image(h, P, words);  // (behind the tile mode: the region's last part depends on it)
+    d.body_flags = h.put(image);  // the image starts with body_flags: the descriptor's table IS the image's head from here on
+    d.tile_image_words = words;
+}
+
+// The tile image: what the Ctx constructor (nt_ctx.hpp) would stage into the block-shared region of a tile, packed once here --
+// the tables of topo_tables(), gshape_param, the gworld gap (the kernels fill it per launch), joint_inc, pair_desc (pair-heavy tile:
+// the hit-list gap), topo_ints() words; then, while params_uniform holds, the parameter copy of a uniform-parameter tile as
+// load_uniform_params lays it out (column 0, effective inverse mass / inertia).  Sized for both parts whatever the flag says now, so
+// that nt_model_refresh_params rewrites it in place.
+std::vector<int32_t> pack_tile_image(nt_model_handle& h, const Params& P, int& words) {
+    const nt_model& d = h.desc;
+    nt_model hd = d;  // the descriptor over the HOST copies of its tables
+    const int32_t** const tabs[NT_TOPO_TABLES] = {
+        &hd.body_flags, &hd.joint_type, &hd.joint_enabled, &hd.joint_parent, &hd.joint_child, &hd.joint_q_start, &hd.joint_qd_start,
+        &hd.joint_tq_start, &hd.joint_lin_count, &hd.joint_ang_count, &hd.shape_body, &hd.shape_type, &hd.shape_flags, &hd.shape_group,
+        &hd.pair_a, &hd.pair_b, &hd.body_joint_start, &hd.body_joint_list, &hd.body_pair_start, &hd.body_pair_list, &hd.shape_mesh_start,
+        &hd.shape_mesh_count, &hd.gshape_id};
+    for (const int32_t** t : tabs) *t = h.host_of(*t).data();
+    const TopoTables tt = topo_tables(hd);
+    const int topo = topo_ints(d);
+    const LdsLayout L = make_layout(d, d.contact_scratch_in_hbm != 0, false, true);
+    std::vector<int32_t> img(((size_t)topo + L.uni_floats + 3) / 4 * 4, 0);
+    int o = 0;
+    for (int k = 0; k < NT_TOPO_TABLES; ++k) {
+        if (tt.len[k]) memcpy(&img[o], tt.src[k], (size_t)tt.len[k] * 4);
+        o += tt.len[k];
+    }
+    if (d.ng) memcpy(&img[o], P.gshape.data(), (size_t)NT_SHAPE_PARAM_FLOATS * d.ng * 4);
+    o += NT_SHAPE_PARAM_FLOATS * d.ng;
+    o += 13 * d.ng;  // gworld
+    {  // joint_inc (Ctx::stage_joint_inc): the last match among the list's real entries
+        const int nlist = d.nj > 0 ? hd.body_joint_start[d.nb] : 0;
+        for (int i = 0; i < 2 * d.nj; ++i) {
+            int at = -1;
+            for (int k = 0; k < nlist; ++k)
+                if (hd.body_joint_list[k] == i) at = k;
+            img[o + i] = at;
+        }
+        o += 2 * d.nj;
+    }
+    if (!d.contact_scratch_in_hbm) {  // pair_desc: the type-sorted shapes, their bodies, bit 30: swapped
+        for (int i = 0; i < d.np; ++i) {
+            int sa = hd.pair_a[i], sb = hd.pair_b[i], swapped = 0;
+            if (hd.shape_type[sa] > hd.shape_type[sb]) { std::swap(sa, sb); swapped = 1; }
+            img[o + 4 * i] = sa; img[o + 4 * i + 1] = sb;
+            img[o + 4 * i + 2] = hd.shape_body[sa];
+            img[o + 4 * i + 3] = (hd.shape_body[sb] & 0x3fffffff) | (swapped << 30);
+        }
+        o += 4 * d.np;
+    } else {
+        o += 1 + d.np;  // hit_count + hit_list
+    }
+    if (o != topo) throw Fail{NT_ERR_INVALID_ARG, "tile image: the topology region does not add up to topo_ints"};
+    words = topo;
+    if (P.uniform) {
+        const size_t ES = d.env_stride;
+        float* up = reinterpret_cast<float*>(&img[topo]);
+        for (int b = 0; b < d.nb; ++b)
+            for (int c = 0; c < NT_BODY_PARAM_FLOATS; ++c) {
+                const bool inv_row = c == BP_INV_MASS || (c >= BP_INV_INERTIA && c < BP_INV_INERTIA + 9);
+                up[L.bp.off + b * NC_BP + c] = inv_row && (hd.body_flags[b] & BODY_KINEMATIC) ? 0.0f : P.body[((size_t)c * d.nb + b) * ES];
+            }
+        for (int j = 0; j < d.nj; ++j)
+            for (int c = 0; c < NT_JOINT_PARAM_FLOATS; ++c) up[L.jp.off + j * NC_JP + c] = P.joint[((size_t)c * d.nj + j) * ES];
+        for (int k = 0; k < d.nd; ++k)
+            for (int c = 0; c < NT_DOF_PARAM_FLOATS; ++c) up[L.dp.off + k * NC_DP + c] = P.dof[((size_t)c * d.nd + k) * ES];
+        for (int s = 0; s < d.ns; ++s)
+            for (int c = 0; c < NT_SHAPE_PARAM_FLOATS; ++c) up[L.sp.off + s * NC_SP + c] = P.shape[((size_t)c * d.ns + s) * ES];
+        words = topo + L.uni_floats;
+    }
+    return img;
 }
 
 template <typename F>
@@ -543,6 +628,7 @@ nt_status nt_model_refresh_params(nt_model_handle* h, const nt_newton_model* src
             if (v.empty()) return;
             if (h->on_device) {
                 if (hipMemcpy((void*)dst, v.data(), v.size() * 4, hipMemcpyHostToDevice) != hipSuccess) throw Fail{NT_ERR_LAUNCH, "hipMemcpy failed"};
+                memcpy(h->host_of(dst).data(), v.data(), v.size() * 4);  // (the host copy the tile image is packed from)
             } else {
                 memcpy((void*)dst, v.data(), v.size() * 4);
             }
@@ -556,6 +642,9 @@ nt_status nt_model_refresh_params(nt_model_handle* h, const nt_newton_model* src
         if (src->joint_enabled && d.nj) update_i(d.joint_enabled, uniform_table(src->joint_enabled, E, d.nj, 0, false, "joint_enabled"));
         if (src->shape_flags) update_i(d.shape_flags, shape_table(src->shape_flags, "shape_flags"));
         if (src->shape_collision_group) update_i(d.shape_group, shape_table(src->shape_collision_group, "shape_collision_group"));
+        int words = 0;
+        update_i(d.body_flags, pack_tile_image(*h, P, words));  // (the image: same sizes, same tile mode, rewritten in place)
+        d.tile_image_words = words;
     });
 }
 

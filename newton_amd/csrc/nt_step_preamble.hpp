@@ -106,8 +106,15 @@ inline int debug_skip() {
 
 // one workgroup per `epb` environments, a.nslot slot-lanes each, `lds_bytes` of dynamic LDS (opted in above the 48 KB default);
 // `extra`: the kernel's arguments behind KArgs
+// NT_TILE_IMAGE=0: the launch goes without the tile image (nt_model.tile_image_words = 0) (the kernels stage the block-shared region from the descriptor's own
+// tables) -- the A/B of the two staging paths within one library, and what the tests hold the image against
+inline bool tile_image_enabled() {
+    const char* e = getenv("NT_TILE_IMAGE");
+    return !(e && e[0] == '0' && e[1] == 0);
+}
 template <typename K, typename... A>
 nt_status launch_tile(K kernel, KArgs a, int epb, size_t lds_bytes, hipStream_t stream, A... extra) {
+    if (!tile_image_enabled()) a.m.tile_image_words = 0;  // (body_flags stays what it is: the image's first table)
 #ifdef NT_ABLATION
     a.debug_skip = debug_skip();
 #endif

@@ -141,7 +141,7 @@ NT_DI void do_fused_substep(const Ctx<EPB>& c, const fused::Ctx<EPB>& cf, bool l
 template <int EPB, bool CVX, bool BIG = false, int THREADS = ((EPB & 255) <= 8 ? 256 : 512), int MINW = 1>
 __global__ void __launch_bounds__(THREADS, MINW) collide_kernel(KArgs a) {
     extern __shared__ __align__(16) float lds[];
-    Ctx<EPB> c(a, lds, -1, BIG);
+    Ctx<EPB> c(a, lds, -1, BIG, true);  // (tile image: committed by load_tile)
     c.lds_records = false;  // (compile-time facts for this kernel: the LDS-record code folds away)
     load_tile(c, &a.s_in, false);
     __syncthreads();
@@ -155,7 +155,7 @@ __global__ void __launch_bounds__(THREADS, MINW) collide_kernel(KArgs a) {
 template <int EPB>
 __global__ void __launch_bounds__((EPB & 255) <= 8 ? 256 : 512) shapes_export_kernel(KArgs a) {
     extern __shared__ __align__(16) float lds[];
-    Ctx<EPB> c(a, lds, -1, false);
+    Ctx<EPB> c(a, lds, -1, false, true);
     c.lds_records = false;
     load_tile(c, &a.s_in, false);
     __syncthreads();
@@ -165,7 +165,7 @@ __global__ void __launch_bounds__((EPB & 255) <= 8 ? 256 : 512) shapes_export_ke
 template <int EPB, bool BIG = false, int THREADS = ((EPB & 255) <= 8 ? 256 : 512), int MINW = 1>
 __global__ void __launch_bounds__(THREADS, MINW) xpbd_step_kernel(KArgs a) {
     extern __shared__ __align__(16) float lds[];
-    Ctx<EPB> c(a, lds, -1, BIG);
+    Ctx<EPB> c(a, lds, -1, BIG, true);  // (tile image: committed by load_tile)
     c.lds_records = false;
     const fused::Ctx<EPB> cf(c, 0);
     load_tile(c, &a.s_in, true);
@@ -218,7 +218,7 @@ template <int EPB, bool CVX, bool BIG = false, int THREADS = ((EPB & 255) <= 8 ?
 __global__ void __launch_bounds__(THREADS, MINW) xpbd_rollout_kernel(KArgs a) {
     extern __shared__ __align__(16) float lds[];
     NT_TICK_START();
-    Ctx<EPB> c(a, lds, -1, BIG);
+    Ctx<EPB> c(a, lds, -1, BIG, true);  // (tile image: committed by load_tile)
     if constexpr (CVX || BIG) c.lds_records = false;  // (granted to analytic-only staged tiles alone: folds the LDS-record code away here)
     c.lane_split = !(CVX || Ctx<EPB>::N >= 32);  // (a compile-time fact per kernel; 32-environment tiles have no idle waves to split onto)
     if constexpr (Ctx<EPB>::SPEC) {  // (granted tile extras and model features the launch code verified: xpbd_spec_tile_fits)
