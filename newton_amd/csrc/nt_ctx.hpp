@@ -1,6 +1,8 @@
 // nt_ctx.hpp -- the per-lane context (Ctx: lane -> (environment, slot), typed LDS accessors, body / shape / dof accessors) and the
 // HBM <-> LDS staging helpers of the fused gfx950 kernels.  No include guard: nt_kernels.hip includes this file once per arithmetic
-// namespace (after nt_layout.hpp), so that Ctx's own arithmetic (w_quad, update_body_derived) follows the namespace's rules.
+// namespace (after nt_layout.hpp), so that Ctx's own arithmetic (Wsym::quad, update_body_derived) follows the namespace's rules.
+// What the block-shared region holds and where is nt_layout.hpp's description (NT_TOPO_TABLE_LIST, topo_region): Ctx binds its pointers to
+// it in one step (bind_topology) and fills it from the host-packed image or table by table.
 // The tile code EPB of every kernel template carries the environments per workgroup in its low byte and the
 // uniform-parameter flag NT_UNI in bit 8: Ctx<EPB>::N is the count, Ctx<EPB>::UNI the flag.
 constexpr int NT_UNI = 256;
@@ -70,14 +72,15 @@ struct Ctx {
         const nt_model& m = a.m;
         R = {wave_up(m.nb), wave_up(m.ns), wave_up(m.np), wave_up(m.nj)};
         ti = reinterpret_cast<int*>(lds + (size_t)rows * N);
-        up = reinterpret_cast<float*>(ti + topo_ints(m));
         gworld_ready = false;
         lane_split = true;
-        has_image = IMAGE && m.tile_image_words >= topo_ints(m);  // (the image then starts at m.body_flags)
+        has_image = IMAGE && m.tile_image_words >= topo_words();  // (the image then starts at m.body_flags)
         img.pending = img.params = false;
-        if constexpr (IMAGE) {
-            if (has_image) issue_image(defer_image);
-            else stage_topology();
+        // (bind_topology runs once on either path: in front of the image's loads, or inside stage_topology behind its batch of 24
+        // loaded values, which is the register peak of several kernels -- profiles/topo_region_resources.txt)
+        if (IMAGE && has_image) {
+            bind_topology();
+            issue_image(defer_image);
         } else {
             stage_topology();
         }
@@ -105,38 +108,40 @@ struct Ctx {
     mutable Image img;
     int* ti;
     bool has_image;
+    // where the parts of the block-shared region live (topo_region, nt_layout.hpp), whichever way they are filled: T.*, `up` behind
+    // them, and the two ranges an image copy leaves unwritten (gworld; the pair-heavy tile's hit list)
+    NT_DI void bind_topology() {
+        const nt_model& m = a.m;
+        const TopoRegion tr = topo_region(m);
+        topo_bind_tables(T, m, ti);
+        T.gshape = reinterpret_cast<float*>(ti + tr.gshape);
+        T.gworld = reinterpret_cast<float*>(ti + tr.gworld);
+        T.joint_inc = ti + tr.joint_inc;
+        T.hit_count = ti + tr.tail;
+        T.hit_list = ti + tr.tail + 1;
+        T.pair_desc = ti + tr.tail;  // (the two tables exclude each other)
+        up = reinterpret_cast<float*>(ti + topo_words());
+        img.g0 = tr.gworld;
+        img.g1 = tr.joint_inc;
+        img.h0 = m.contact_scratch_in_hbm ? tr.tail : tr.total;
+        img.h1 = tr.total;
+    }
+    // words of the region.  The tiles that never take the image use the closed form: with `up` derived from the walked sum the
+    // substep loop of the 32-wide XPBD rollout reloads more spilled scalars, -4.5 % at 8 192 environments; the image tiles keep the
+    // walked total, with which the tile of 16 measures as before (profiles/topo_region_ab.txt)
+    NT_DI int topo_words() const { return IMAGE ? topo_region(a.m).total : topo_ints(a.m); }
+    // a kernel's own block-shared tables: n ints just behind the topology; the uniform parameter copy moves behind them
+    NT_DI int* own_tables(const int n) {
+        int* const tab = ti + topo_words();
+        up = reinterpret_cast<float*>(tab + n);
+        return tab;
+    }
     NT_DI void issue_image(const bool defer) {
         const nt_model& m = a.m;
-        const TopoTables tt = topo_tables(m);
-        const int** const dsts[NT_TOPO_TABLES] = {
-            &T.body_flags, &T.joint_type, &T.joint_enabled, &T.joint_parent, &T.joint_child, &T.joint_q_start, &T.joint_qd_start,
-            &T.joint_tq_start, &T.joint_lin_count, &T.joint_ang_count, &T.shape_body, &T.shape_type, &T.shape_flags, &T.shape_group,
-            &T.pair_a, &T.pair_b, &T.body_joint_start, &T.body_joint_list, &T.body_pair_start, &T.body_pair_list, &T.shape_mesh_start,
-            &T.shape_mesh_count, &T.gshape_id};
-        int o = 0;
-#pragma unroll
-        for (int k = 0; k < NT_TOPO_TABLES; ++k) {
-            *dsts[k] = ti + o;
-            o += tt.len[k];
-        }
-        T.gshape = reinterpret_cast<float*>(ti + o);
-        o += NT_SHAPE_PARAM_FLOATS * m.ng;
-        T.gworld = reinterpret_cast<float*>(ti + o);
-        img.g0 = o;
-        o += 13 * m.ng;
-        img.g1 = o;
-        T.joint_inc = ti + o;
-        o += 2 * m.nj;
-        T.hit_count = ti + o;
-        T.hit_list = ti + o + 1;
-        T.pair_desc = ti + o;  // (the two tables exclude each other)
-        const int topo = topo_ints(m);
-        img.h0 = m.contact_scratch_in_hbm ? o : topo;
-        img.h1 = topo;
-        img.total = topo;
+        img.total = img.h1;
         if constexpr (UNI) {
-            if (defer && m.tile_image_words >= topo + L.uni_floats) {
-                img.total = topo + L.uni_floats;
+            if (defer && m.tile_image_words >= img.total + L.uni_floats) {
+                img.total += L.uni_floats;
                 img.params = true;
             }
         }
@@ -177,54 +182,26 @@ struct Ctx {
         // written to LDS afterwards.  (One copy loop per table compiles to load / s_waitcnt vmcnt(0) / ds_write per table: 24
         // serialised memory round trips, ~25 us per launch -- most of what a per-call collide / step kernel took, 8 % of a
         // 10-substep rollout launch.)  Tables longer than the workgroup finish in a tail loop.
-        const int32_t* const srcs[NT_TOPO_TABLES] = {
-            m.body_flags, m.joint_type, m.joint_enabled, m.joint_parent, m.joint_child, m.joint_q_start, m.joint_qd_start, m.joint_tq_start,
-            m.joint_lin_count, m.joint_ang_count, m.shape_body, m.shape_type, m.shape_flags, m.shape_group, m.pair_a, m.pair_b,
-            m.body_joint_start, m.body_joint_list, m.body_pair_start, m.body_pair_list, m.shape_mesh_start, m.shape_mesh_count, m.gshape_id};
-        const int nsg = m.ns + m.ng;
-        const int lens[NT_TOPO_TABLES] = {m.nb, m.nj, m.nj, m.nj, m.nj, m.nj, m.nj, m.nj, m.nj, m.nj, nsg, nsg, nsg, nsg, m.np, m.np,
-                                          m.nb + 1, 2 * m.nj /* padded by the host */, m.nb + 1, 2 * m.np /* padded */, nsg, nsg, m.ng};
-        const int** const dsts[NT_TOPO_TABLES] = {
-            &T.body_flags, &T.joint_type, &T.joint_enabled, &T.joint_parent, &T.joint_child, &T.joint_q_start, &T.joint_qd_start,
-            &T.joint_tq_start, &T.joint_lin_count, &T.joint_ang_count, &T.shape_body, &T.shape_type, &T.shape_flags, &T.shape_group,
-            &T.pair_a, &T.pair_b, &T.body_joint_start, &T.body_joint_list, &T.body_pair_start, &T.body_pair_list, &T.shape_mesh_start,
-            &T.shape_mesh_count, &T.gshape_id};
+        const TopoTables tt = topo_tables(m);
         int first[NT_TOPO_TABLES];
         const int tid = threadIdx.x;
 #pragma unroll
-        for (int k = 0; k < NT_TOPO_TABLES; ++k) first[k] = tid < lens[k] ? srcs[k][tid] : 0;
+        for (int k = 0; k < NT_TOPO_TABLES; ++k) first[k] = tid < tt.len[k] ? tt.src[k][tid] : 0;
         const int ngf = NT_SHAPE_PARAM_FLOATS * m.ng;
         const float gfirst = tid < ngf ? m.gshape_param[tid] : 0.0f;
 #pragma unroll
         for (int k = 0; k < NT_TOPO_TABLES; ++k) {
-            if (tid < lens[k]) ti[o + tid] = first[k];
-            for (int i = tid + (int)blockDim.x; i < lens[k]; i += blockDim.x) ti[o + i] = srcs[k][i];
-            *dsts[k] = ti + o;
-            o += lens[k];
+            if (tid < tt.len[k]) ti[o + tid] = first[k];
+            for (int i = tid + (int)blockDim.x; i < tt.len[k]; i += blockDim.x) ti[o + i] = tt.src[k][i];
+            o += tt.len[k];
         }
-        {
-            float* g = reinterpret_cast<float*>(ti + o);
-            if (tid < ngf) g[tid] = gfirst;
-            for (int i = tid + (int)blockDim.x; i < ngf; i += blockDim.x) g[i] = m.gshape_param[i];
-            T.gshape = g;
-            o += ngf;
-        }
-        T.gworld = reinterpret_cast<float*>(ti + o);
-        o += 13 * m.ng;
-        T.joint_inc = ti + o;  // (filled by stage_joint_inc, one barrier after the tables above are published)
-        o += 2 * m.nj;
-        T.hit_count = ti + o;
-        T.hit_list = ti + o + 1;
-        T.pair_desc = ti + o;  // (the two tables exclude each other)
-        if (!m.contact_scratch_in_hbm) {
-            for (int i = threadIdx.x; i < m.np; i += blockDim.x) {
-                int sa = m.pair_a[i], sb = m.pair_b[i], swapped = 0;
-                if (m.shape_type[sa] > m.shape_type[sb]) { const int t_ = sa; sa = sb; sb = t_; swapped = 1; }
-                ti[o + 4 * i] = sa; ti[o + 4 * i + 1] = sb;
-                ti[o + 4 * i + 2] = m.shape_body[sa];
-                ti[o + 4 * i + 3] = (m.shape_body[sb] & 0x3fffffff) | (swapped << 30);
-            }
-        }
+        float* g = reinterpret_cast<float*>(ti + o);  // (behind the tables: what bind_topology makes T.gshape)
+        if (tid < ngf) g[tid] = gfirst;
+        for (int i = tid + (int)blockDim.x; i < ngf; i += blockDim.x) g[i] = m.gshape_param[i];
+        bind_topology();
+        // (joint_inc is filled by stage_joint_inc, one barrier after the tables above are published)
+        if (!m.contact_scratch_in_hbm)
+            for (int i = threadIdx.x; i < m.np; i += blockDim.x) pair_desc_words(m, i, const_cast<int*>(T.pair_desc) + 4 * i);
     }
     // the same lane seen from the other arithmetic namespace (ieee::Ctx <-> fused::Ctx): no staging, every member copied
     template <class OtherCtx>
@@ -314,12 +291,7 @@ struct Ctx {
         if (has_image) return;  // (the image carries the table)
         const int nlist = a.m.nj > 0 ? T.body_joint_start[a.m.nb] : 0;
         int* inv = const_cast<int*>(T.joint_inc);
-        for (int i = threadIdx.x; i < 2 * a.m.nj; i += blockDim.x) {
-            int at = -1;
-            for (int k = 0; k < nlist; ++k)
-                if (T.body_joint_list[k] == i) at = k;
-            inv[i] = at;
-        }
+        for (int i = threadIdx.x; i < 2 * a.m.nj; i += blockDim.x) inv[i] = joint_inc_entry(T.body_joint_list, nlist, i);
     }
     NT_DI xform body_q(int b) const { return lxf(L.bq, 0, a.m.nb, b); }
     NT_DI xform body_q_in(int b) const { return lxf(Fld<7>{pose_in_off}, 0, a.m.nb, b); }
@@ -334,7 +306,8 @@ struct Ctx {
     NT_DI mat33 inertia(int b) const { return plm33(L.bp, BP_INERTIA, a.m.nb, b); }
     NT_DI vec3 com(int b) const { return plv3(L.bp, BP_COM, a.m.nb, b); }
     NT_DI vec3 world_com(int b) const { return lv3(L.bd, 0, a.m.nb, b); }
-    // the world-frame inverse inertia tile of body b as a value (six floats fetched once, then any number of quadratic forms)
+    // the world-frame inverse inertia tile R I^-1 R^T of body b as a value (six floats fetched once, then any number of quadratic
+    // forms v^T W v)
     struct Wsym {
         float xx, xy, xz, yy, yz, zz;
         NT_DI float quad(vec3 v) const {
@@ -345,14 +318,6 @@ struct Ctx {
     NT_DI Wsym w_tile(int b) const {
         const int nb = a.m.nb;
         return Wsym{l(L.bd, 3, nb, b), l(L.bd, 4, nb, b), l(L.bd, 5, nb, b), l(L.bd, 6, nb, b), l(L.bd, 7, nb, b), l(L.bd, 8, nb, b)};
-    }
-    // a^T (R I^-1 R^T) a for body b (world-frame inverse inertia, symmetric 6-float tile in LDS)
-    NT_DI float w_quad(int b, vec3 v) const {
-        const int nb = a.m.nb;
-        float xx = l(L.bd, 3, nb, b), xy = l(L.bd, 4, nb, b), xz = l(L.bd, 5, nb, b);
-        float yy = l(L.bd, 6, nb, b), yz = l(L.bd, 7, nb, b), zz = l(L.bd, 8, nb, b);
-        vec3 wv(xx * v.x + xy * v.y + xz * v.z, xy * v.x + yy * v.y + yz * v.z, xz * v.x + yz * v.y + zz * v.z);
-        return dot(v, wv);
     }
     NT_DI void update_body_derived(int b) const {
         xform X = body_q(b);
@@ -411,10 +376,11 @@ struct Ctx {
 // ------------------------------------------------------------------------------------------------
 // field [ncomp][n][ES] in HBM <-> slot-major rows in LDS
 // (loads in batches of eight before the LDS writes: a load / wait / write per row is one memory round trip per row)
+// first: the first item of the lane's walk -- c.slot, or c.slot + c.nslot behind a first trip that load_tile fetched itself
 constexpr int NT_STAGE_BATCH = 8;
 template <int EPB, int NC>
-NT_DI void stage_rows(const Ctx<EPB>& c, Fld<NC> f, const float* src, int ncomp, int n) {
-    for (int s = c.slot; s < n; s += c.nslot)
+NT_DI void stage_rows(const Ctx<EPB>& c, Fld<NC> f, const float* src, int ncomp, int n, int first) {
+    for (int s = first; s < n; s += c.nslot)
         for (int c0 = 0; c0 < ncomp; c0 += NT_STAGE_BATCH) {
             float v[NT_STAGE_BATCH];
 #pragma unroll
@@ -445,12 +411,28 @@ template <int EPB>
 NT_DI void unstage_rows(const Ctx<EPB>& c, int lds_off, float* dst, int rows) {
     for (int r = c.slot; r < rows; r += c.nslot) dst[(size_t)r * c.ES + c.env] = c.lds[(lds_off + r) * Ctx<EPB>::N + c.e];
 }
+// the body parameters of the lane's environment from item `first` on, inverse mass / inertia as effective_body_param gives them
+// (flags from the descriptor's table: the LDS topology may not be published yet); BATCH components' loads leave together
+template <int BATCH, int EPB>
+NT_DI void stage_body_params(const Ctx<EPB>& c, int first) {
+    const nt_model& m = c.a.m;
+    for (int b = first; b < m.nb; b += c.nslot)
+        for (int c0 = 0; c0 < NT_BODY_PARAM_FLOATS; c0 += BATCH) {
+            float v[BATCH];
+#pragma unroll
+            for (int k = 0; k < BATCH; ++k)
+                v[k] = c0 + k < NT_BODY_PARAM_FLOATS ? effective_body_param(c0 + k, m.body_flags[b], m.body_param[c.g(c0 + k, m.nb, b)]) : 0.0f;
+#pragma unroll
+            for (int k = 0; k < BATCH; ++k)
+                if (c0 + k < NT_BODY_PARAM_FLOATS) c.l(c.L.bp, c0 + k, m.nb, b) = v[k];
+        }
+}
 
 template <int EPB>
 NT_DI void load_state(const Ctx<EPB>& c, const nt_state& s) {
     if (!c.valid) return;
-    stage_rows(c, c.L.bq, s.body_q, 7, c.a.m.nb);
-    stage_rows(c, c.L.bqd, s.body_qd, 6, c.a.m.nb);
+    stage_rows(c, c.L.bq, s.body_q, 7, c.a.m.nb, c.slot);
+    stage_rows(c, c.L.bqd, s.body_qd, 6, c.a.m.nb, c.slot);
 }
 template <int EPB>
 NT_DI void store_state(const Ctx<EPB>& c, const nt_state& s) {
@@ -460,7 +442,7 @@ NT_DI void store_state(const Ctx<EPB>& c, const nt_state& s) {
 }
 // ---- first-trip batches: the first item a lane owns in a field (s = slot), all components at once.  A kernel's whole tile -- state,
 // parameters, controls -- is fetched as ONE batch of loads followed by the LDS writes (load_tile); items beyond the first trip
-// (fields longer than the slot-thread count) follow through stage_rows_rest.
+// (fields longer than the slot-thread count) follow through stage_rows / stage_body_params from c.slot + c.nslot.
 template <int NCOMP, int EPB>
 NT_DI void first_load(const Ctx<EPB>& c, const float* src, int n, float (&v)[NCOMP]) {
 #pragma unroll
@@ -473,83 +455,51 @@ NT_DI void first_store(const Ctx<EPB>& c, Fld<NC> f, int n, const float (&v)[NCO
         for (int k = 0; k < NCOMP; ++k) c.l(f, k, n, c.slot) = v[k];
     }
 }
-template <int EPB, int NC>
-NT_DI void stage_rows_rest(const Ctx<EPB>& c, Fld<NC> f, const float* src, int ncomp, int n) {
-    for (int s = c.slot + c.nslot; s < n; s += c.nslot)
-        for (int c0 = 0; c0 < ncomp; c0 += NT_STAGE_BATCH) {
-            float v[NT_STAGE_BATCH];
-#pragma unroll
-            for (int k = 0; k < NT_STAGE_BATCH; ++k) v[k] = c0 + k < ncomp ? src[c.g(c0 + k, n, s)] : 0.0f;
-#pragma unroll
-            for (int k = 0; k < NT_STAGE_BATCH; ++k)
-                if (c0 + k < ncomp) c.l(f, c0 + k, n, s) = v[k];
-        }
-}
 
 // the block-shared parameter copy of a uniform-parameter tile: one copy per workgroup, read from the tile's first environment (the
-// host vouches that all columns are equal).  Only where the tile image does not hold the copy
+// host vouches that all columns are equal), laid out by uni_word.  Only where the tile image does not hold the copy
 template <int EPB>
 NT_DI void load_uniform_params(const Ctx<EPB>& c) {
     if (c.img.params) return;  // (the tile image carried the copy: nt_model.tile_image_words)
     const nt_model& m = c.a.m;
-    const int nb = m.nb;
-    auto body_value = [&](int comp, int b, size_t col) {
-        float v = m.body_param[(size_t)(comp * nb + b) * c.ES + col];
-        bool inv_row = comp == BP_INV_MASS || (comp >= BP_INV_INERTIA && comp < BP_INV_INERTIA + 9);
-        if (inv_row && (m.body_flags[b] & BODY_KINEMATIC)) v = 0.0f;  // (global copy: the LDS topology is not published yet)
-        return v;
-    };
     const size_t col = (size_t)blockIdx.x * Ctx<EPB>::N;
-    const int nbp = NT_BODY_PARAM_FLOATS * nb, njp = NT_JOINT_PARAM_FLOATS * m.nj, ndp = NT_DOF_PARAM_FLOATS * m.nd,
+    auto at = [&](const float* table, int r) { return table[(size_t)r * c.ES + col]; };
+    // (flags from the descriptor's table: the LDS topology is not published yet)
+    auto body = [&](int r) { return effective_body_param(r / m.nb, m.body_flags[r % m.nb], at(m.body_param, r)); };
+    const int nbp = NT_BODY_PARAM_FLOATS * m.nb, njp = NT_JOINT_PARAM_FLOATS * m.nj, ndp = NT_DOF_PARAM_FLOATS * m.nd,
               nsp = NT_SHAPE_PARAM_FLOATS * m.ns;
-    const int r0 = threadIdx.x;
+    const int r0 = threadIdx.x, step = blockDim.x;
     // first trip of the four tables as one batch of loads, then the rest
-    const float vb = r0 < nbp ? body_value(r0 / nb, r0 % nb, col) : 0.0f;
-    const float vj = r0 < njp ? m.joint_param[(size_t)r0 * c.ES + col] : 0.0f;
-    const float vd = r0 < ndp ? m.dof_param[(size_t)r0 * c.ES + col] : 0.0f;
-    const float vs = r0 < nsp ? m.shape_param[(size_t)r0 * c.ES + col] : 0.0f;
-    if (r0 < nbp) c.up[c.L.bp.off + (r0 % nb) * NC_BP + r0 / nb] = vb;
-    if (r0 < njp) c.up[c.L.jp.off + (r0 % m.nj) * NC_JP + r0 / m.nj] = vj;
-    if (r0 < ndp) c.up[c.L.dp.off + (r0 % m.nd) * NC_DP + r0 / m.nd] = vd;
-    if (r0 < nsp) c.up[c.L.sp.off + (r0 % m.ns) * NC_SP + r0 / m.ns] = vs;
-    for (int r = r0 + blockDim.x; r < nbp; r += blockDim.x) c.up[c.L.bp.off + (r % nb) * NC_BP + r / nb] = body_value(r / nb, r % nb, col);
-    for (int r = r0 + blockDim.x; r < njp; r += blockDim.x) c.up[c.L.jp.off + (r % m.nj) * NC_JP + r / m.nj] = m.joint_param[(size_t)r * c.ES + col];
-    for (int r = r0 + blockDim.x; r < ndp; r += blockDim.x) c.up[c.L.dp.off + (r % m.nd) * NC_DP + r / m.nd] = m.dof_param[(size_t)r * c.ES + col];
-    for (int r = r0 + blockDim.x; r < nsp; r += blockDim.x) c.up[c.L.sp.off + (r % m.ns) * NC_SP + r / m.ns] = m.shape_param[(size_t)r * c.ES + col];
+    const float vb = r0 < nbp ? body(r0) : 0.0f;
+    const float vj = r0 < njp ? at(m.joint_param, r0) : 0.0f;
+    const float vd = r0 < ndp ? at(m.dof_param, r0) : 0.0f;
+    const float vs = r0 < nsp ? at(m.shape_param, r0) : 0.0f;
+    if (r0 < nbp) c.up[uni_word(c.L.bp, r0, m.nb)] = vb;
+    if (r0 < njp) c.up[uni_word(c.L.jp, r0, m.nj)] = vj;
+    if (r0 < ndp) c.up[uni_word(c.L.dp, r0, m.nd)] = vd;
+    if (r0 < nsp) c.up[uni_word(c.L.sp, r0, m.ns)] = vs;
+    for (int r = r0 + step; r < nbp; r += step) c.up[uni_word(c.L.bp, r, m.nb)] = body(r);
+    for (int r = r0 + step; r < njp; r += step) c.up[uni_word(c.L.jp, r, m.nj)] = at(m.joint_param, r);
+    for (int r = r0 + step; r < ndp; r += step) c.up[uni_word(c.L.dp, r, m.nd)] = at(m.dof_param, r);
+    for (int r = r0 + step; r < nsp; r += step) c.up[uni_word(c.L.sp, r, m.ns)] = at(m.shape_param, r);
 }
 // parameters and controls: read once per kernel
 template <int EPB>
 NT_DI void load_params(const Ctx<EPB>& c, bool with_control) {
     const nt_model& m = c.a.m;
-    const int nb = m.nb;
-    // body params carry the effective (kinematic => 0) inverse mass / inertia (solver.py:173-187)
-    auto body_value = [&](int comp, int b, size_t col) {
-        float v = m.body_param[(size_t)(comp * nb + b) * c.ES + col];
-        bool inv_row = comp == BP_INV_MASS || (comp >= BP_INV_INERTIA && comp < BP_INV_INERTIA + 9);
-        if (inv_row && (m.body_flags[b] & BODY_KINEMATIC)) v = 0.0f;  // (global copy: the LDS topology is not published yet)
-        return v;
-    };
     if constexpr (Ctx<EPB>::UNI) load_uniform_params(c);
     if (!c.valid) return;
     if constexpr (!Ctx<EPB>::UNI) {
-        for (int b = c.slot; b < nb; b += c.nslot)
-            for (int c0 = 0; c0 < NT_BODY_PARAM_FLOATS; c0 += NT_STAGE_BATCH) {
-                float v[NT_STAGE_BATCH];
-#pragma unroll
-                for (int k = 0; k < NT_STAGE_BATCH; ++k) v[k] = c0 + k < NT_BODY_PARAM_FLOATS ? body_value(c0 + k, b, c.env) : 0.0f;
-#pragma unroll
-                for (int k = 0; k < NT_STAGE_BATCH; ++k)
-                    if (c0 + k < NT_BODY_PARAM_FLOATS) c.lds[(c.L.bp.off + b * NC_BP + c0 + k) * Ctx<EPB>::N + c.e] = v[k];
-            }
-        stage_rows(c, c.L.jp, m.joint_param, NT_JOINT_PARAM_FLOATS, m.nj);
-        stage_rows(c, c.L.dp, m.dof_param, NT_DOF_PARAM_FLOATS, m.nd);
-        stage_rows(c, c.L.sp, m.shape_param, NT_SHAPE_PARAM_FLOATS, m.ns);
+        stage_body_params<NT_STAGE_BATCH>(c, c.slot);
+        stage_rows(c, c.L.jp, m.joint_param, NT_JOINT_PARAM_FLOATS, m.nj, c.slot);
+        stage_rows(c, c.L.dp, m.dof_param, NT_DOF_PARAM_FLOATS, m.nd, c.slot);
+        stage_rows(c, c.L.sp, m.shape_param, NT_SHAPE_PARAM_FLOATS, m.ns, c.slot);
     }
-    stage_rows(c, c.L.grav, m.gravity, 3, 1);
+    stage_rows(c, c.L.grav, m.gravity, 3, 1, c.slot);
     if (with_control) {
-        stage_rows(c, c.L.cf, c.a.c.joint_f, 1, m.nd);
-        stage_rows(c, c.L.ctq, c.a.c.joint_target_q, 1, m.ntq);
-        stage_rows(c, c.L.ctqd, c.a.c.joint_target_qd, 1, m.nd);
+        stage_rows(c, c.L.cf, c.a.c.joint_f, 1, m.nd, c.slot);
+        stage_rows(c, c.L.ctq, c.a.c.joint_target_q, 1, m.ntq, c.slot);
+        stage_rows(c, c.L.ctqd, c.a.c.joint_target_qd, 1, m.nd, c.slot);
     }
 }
 
@@ -594,11 +544,8 @@ NT_DI void load_tile(const Ctx<EPB>& c, const nt_state* state, bool with_control
         first_store(c, c.L.bqd, nb, vqd);
     }
     if constexpr (!UNI) {
-        if (flags & BODY_KINEMATIC) {  // effective (kinematic => 0) inverse mass / inertia (solver.py:173-187)
-            vbp[BP_INV_MASS] = 0.0f;
 #pragma unroll
-            for (int k = 0; k < 9; ++k) vbp[BP_INV_INERTIA + k] = 0.0f;
-        }
+        for (int k = 0; k < NT_BODY_PARAM_FLOATS; ++k) vbp[k] = effective_body_param(k, flags, vbp[k]);
         first_store(c, c.L.bp, nb, vbp);
         first_store(c, c.L.jp, m.nj, vjp);
         first_store(c, c.L.dp, m.nd, vdp);
@@ -613,25 +560,20 @@ NT_DI void load_tile(const Ctx<EPB>& c, const nt_state* state, bool with_control
         if (c.slot < m.ntq) c.l(c.L.ctq, 0, m.ntq, c.slot) = vctq;
     }
     // ---- items beyond the first trip
+    const int rest = c.slot + c.nslot;
     if (state) {
-        stage_rows_rest(c, c.L.bq, state->body_q, 7, nb);
-        stage_rows_rest(c, c.L.bqd, state->body_qd, 6, nb);
+        stage_rows(c, c.L.bq, state->body_q, 7, nb, rest);
+        stage_rows(c, c.L.bqd, state->body_qd, 6, nb, rest);
     }
     if constexpr (!UNI) {
-        for (int b = c.slot + c.nslot; b < nb; b += c.nslot)
-            for (int comp = 0; comp < NT_BODY_PARAM_FLOATS; ++comp) {
-                float v = m.body_param[(size_t)(comp * nb + b) * c.ES + c.env];
-                const bool inv_row = comp == BP_INV_MASS || (comp >= BP_INV_INERTIA && comp < BP_INV_INERTIA + 9);
-                if (inv_row && (m.body_flags[b] & BODY_KINEMATIC)) v = 0.0f;
-                c.lds[(c.L.bp.off + b * NC_BP + comp) * Ctx<EPB>::N + c.e] = v;
-            }
-        stage_rows_rest(c, c.L.jp, m.joint_param, NT_JOINT_PARAM_FLOATS, m.nj);
-        stage_rows_rest(c, c.L.dp, m.dof_param, NT_DOF_PARAM_FLOATS, m.nd);
-        stage_rows_rest(c, c.L.sp, m.shape_param, NT_SHAPE_PARAM_FLOATS, m.ns);
+        stage_body_params<1>(c, rest);  // (one component at a time: a batch of eight here is unmeasured in the rollout kernels)
+        stage_rows(c, c.L.jp, m.joint_param, NT_JOINT_PARAM_FLOATS, m.nj, rest);
+        stage_rows(c, c.L.dp, m.dof_param, NT_DOF_PARAM_FLOATS, m.nd, rest);
+        stage_rows(c, c.L.sp, m.shape_param, NT_SHAPE_PARAM_FLOATS, m.ns, rest);
     }
     if (with_control) {
-        stage_rows_rest(c, c.L.cf, c.a.c.joint_f, 1, m.nd);
-        stage_rows_rest(c, c.L.ctq, c.a.c.joint_target_q, 1, m.ntq);
-        stage_rows_rest(c, c.L.ctqd, c.a.c.joint_target_qd, 1, m.nd);
+        stage_rows(c, c.L.cf, c.a.c.joint_f, 1, m.nd, rest);
+        stage_rows(c, c.L.ctq, c.a.c.joint_target_q, 1, m.ntq, rest);
+        stage_rows(c, c.L.ctqd, c.a.c.joint_target_qd, 1, m.nd, rest);
     }
 }

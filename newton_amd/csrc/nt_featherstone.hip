@@ -435,7 +435,7 @@ NT_DI int jm_max_joints(const nt_model& m) {
 template <int EPB>
 NT_DI void jm_load(const Ctx<EPB>& c, const JmLayout& F) {
     const nt_model& m = c.a.m;
-    if (c.valid) stage_rows(c, c.L.bq, c.a.s_in.body_q, 7, m.nb);
+    if (c.valid) stage_rows(c, c.L.bq, c.a.s_in.body_q, 7, m.nb, c.slot);
     load_params(c, false);
     if (c.valid) stage_rows(c, F.jq, c.a.s_in.joint_q, m.nc);
 }
@@ -448,8 +448,7 @@ __global__ void __launch_bounds__(256) eval_jacobian_kernel(KArgs a, float* J, f
     constexpr int N = Ctx<EPB>::N;
     const JmLayout F = jm_layout(m, Ctx<EPB>::UNI, false);
     Ctx<EPB> c(a, lds, F.rows);
-    int* extra = reinterpret_cast<int*>(lds + (size_t)F.rows * N) + topo_ints(m);
-    c.up = reinterpret_cast<float*>(extra + jm_table_ints(m));
+    int* extra = c.own_tables(jm_table_ints(m));
     __syncthreads();
     jm_build_tables(c, extra);
     const JmCtx<EPB> f(c, F, extra);
@@ -535,8 +534,7 @@ __global__ void __launch_bounds__(256) eval_mass_matrix_kernel(KArgs a, float* H
     constexpr int N = Ctx<EPB>::N;
     const JmLayout F = jm_layout(m, Ctx<EPB>::UNI, true);
     Ctx<EPB> c(a, lds, F.rows);
-    int* extra = reinterpret_cast<int*>(lds + (size_t)F.rows * N) + topo_ints(m);
-    c.up = reinterpret_cast<float*>(extra + jm_table_ints(m));
+    int* extra = c.own_tables(jm_table_ints(m));
     __syncthreads();
     jm_build_tables(c, extra);
     const JmCtx<EPB> f(c, F, extra);
@@ -857,12 +855,10 @@ __global__ void __launch_bounds__(256) ik_solve_kernel(KArgs a, nt_ik_problem P,
                                                        float* cost, int iterations, float step) {
     extern __shared__ __align__(16) float lds[];
     const nt_model& m = a.m;
-    constexpr int N = Ctx<EPB>::N;
     const IksLayout F = iks_layout(m, P, Ctx<EPB>::UNI);
     Ctx<EPB> c(a, lds, F.rows);
-    int* extra = reinterpret_cast<int*>(lds + (size_t)F.rows * N) + topo_ints(m);
+    int* extra = c.own_tables(iks_table_ints(m));
     int* tab = extra + jm_table_ints(m);
-    c.up = reinterpret_cast<float*>(extra + iks_table_ints(m));
     __syncthreads();
     jm_build_tables(c, extra);
     const JmCtx<EPB> f(c, F.J, extra);

@@ -10,13 +10,7 @@ template <int EPB>
 NT_DI FsLayout fs_kernel_layout(const KArgs& a) {
     return make_fs_layout(a.m, make_layout(a.m, false, false, Ctx<EPB>::UNI, false), fs_tree_mode(a));
 }
-// workgroup memory: [F.rows x N floats][topology ints][Featherstone ints][uniform-parameter floats]
-template <int EPB>
-NT_DI int* fs_place_tables(Ctx<EPB>& c, float* lds, const FsLayout& F) {
-    int* extra = reinterpret_cast<int*>(lds + (size_t)F.rows * Ctx<EPB>::N) + topo_ints(c.a.m);
-    c.up = reinterpret_cast<float*>(extra + fs_topo_ints(c.a.m));  // (Ctx put it behind the topology ints, where `extra` lives here)
-    return extra;
-}
+// workgroup memory: [F.rows x N floats][topology ints][Featherstone ints (Ctx::own_tables)][uniform-parameter floats]
 
 template <int EPB>
 __global__ void __launch_bounds__(256) featherstone_step_kernel(KArgs a) {
@@ -24,7 +18,7 @@ __global__ void __launch_bounds__(256) featherstone_step_kernel(KArgs a) {
     const nt_model& m = a.m;
     const FsLayout F = fs_kernel_layout<EPB>(a);
     Ctx<EPB> c(a, lds, F.rows);  // topology ints are staged behind the Featherstone rows
-    int* extra = fs_place_tables(c, lds, F);
+    int* extra = c.own_tables(fs_topo_ints(m));
     __syncthreads();
     fs_build_tables(c, extra);
     FsCtx<EPB> f(c, extra);
@@ -54,7 +48,7 @@ __global__ void __launch_bounds__(THREADS) featherstone_rollout_kernel(KArgs a) 
     const nt_model& m = a.m;
     const FsLayout F = fs_kernel_layout<EPB>(a);
     Ctx<EPB> c(a, lds, F.rows);
-    int* extra = fs_place_tables(c, lds, F);
+    int* extra = c.own_tables(fs_topo_ints(m));
     __syncthreads();
     fs_build_tables(c, extra);
     FsCtx<EPB> f(c, extra);
@@ -97,7 +91,7 @@ __global__ void __launch_bounds__(256) eval_fk_kernel(KArgs a, const float* join
     const int nj = m.nj;
     const FsLayout F = fs_kernel_layout<EPB>(a);
     Ctx<EPB> c(a, lds, F.rows);
-    int* extra = fs_place_tables(c, lds, F);
+    int* extra = c.own_tables(fs_topo_ints(m));
     __syncthreads();
     for (int j = threadIdx.x; j < nj; j += blockDim.x) {
         int p = c.T.joint_parent[j], anc = -1;

@@ -1,5 +1,6 @@
-// nt_layout.hpp -- row constants, LDS layout, kernel arguments and the block-shared topology tables of the fused gfx950 kernels:
-// everything that carries no vector-math type.  The per-lane context (Ctx) and the HBM <-> LDS staging helpers are nt_ctx.hpp.
+// nt_layout.hpp -- row constants, LDS layout, kernel arguments and the one description of the tile's block-shared region (table list,
+// offsets, the encodings of its derived tables) of the fused gfx950 kernels: everything that carries no vector-math type.  The
+// per-lane context (Ctx) and the HBM <-> LDS staging helpers are nt_ctx.hpp.
 // Included ONCE by nt_kernels.hip at the top of its anonymous namespace; nt_ctx.hpp / nt_xpbd.hpp are then included once per
 // arithmetic namespace (`ieee`: nt:: helpers, no contraction; `fused`: ntf:: helpers, a * b + c may contract -- see nt_kernels.hip).
 #pragma once
@@ -212,11 +213,28 @@ struct KArgs {
 #endif
 };
 
-// env-uniform topology, staged once per workgroup into LDS (block-shared ints behind the per-env rows)
+// The block-shared region of a tile: env-uniform ints behind the per-env rows, written once per workgroup.  Its order and sizes are
+// written down HERE and nowhere else: the tables of NT_TOPO_TABLE_LIST, then the parts topo_region() places -- gshape
+// [NT_SHAPE_PARAM_FLOATS ng], gworld [13 ng], joint_inc [2 nj], and the tail: pair_desc [4 np] or (pair-heavy tile) hit_count +
+// hit_list [1 + np]; the parameter copy of a uniform-parameter tile follows.  Both staging paths of Ctx (nt_ctx.hpp) and the host's
+// tile image (nt_model.tile_image_words, pack_tile_image in nt_model_build.hip) walk this description.
+// (member of Topo = field of nt_model, length in ints; the two incidence lists are padded to their length by the host)
+#define NT_TOPO_TABLE_LIST(X)                                                                                              \
+    X(body_flags, m.nb)                                                                                                    \
+    X(joint_type, m.nj) X(joint_enabled, m.nj) X(joint_parent, m.nj) X(joint_child, m.nj) X(joint_q_start, m.nj)           \
+    X(joint_qd_start, m.nj) X(joint_tq_start, m.nj) X(joint_lin_count, m.nj) X(joint_ang_count, m.nj)                      \
+    X(shape_body, m.ns + m.ng) X(shape_type, m.ns + m.ng) X(shape_flags, m.ns + m.ng) X(shape_group, m.ns + m.ng)          \
+    X(pair_a, m.np) X(pair_b, m.np)                                                                                        \
+    X(body_joint_start, m.nb + 1) X(body_joint_list, 2 * m.nj) X(body_pair_start, m.nb + 1) X(body_pair_list, 2 * m.np)    \
+    X(shape_mesh_start, m.ns + m.ng) X(shape_mesh_count, m.ns + m.ng) X(gshape_id, m.ng)
+#define NT_TOPO_COUNT(name, len) +1
+#define NT_TOPO_MEMBER(name, len) const int* name;
+#define NT_TOPO_SRC(name, len) m.name,
+#define NT_TOPO_LEN(name, len) len,
+#define NT_TOPO_BIND(name, len) T.name = base + o; o += len;
+constexpr int NT_TOPO_TABLES = 0 NT_TOPO_TABLE_LIST(NT_TOPO_COUNT);
 struct Topo {
-    const int *body_flags, *joint_type, *joint_enabled, *joint_parent, *joint_child, *joint_q_start, *joint_qd_start,
-        *joint_tq_start, *joint_lin_count, *joint_ang_count, *shape_body, *shape_type, *shape_flags, *shape_group, *pair_a,
-        *pair_b, *body_joint_start, *body_joint_list, *body_pair_start, *body_pair_list, *shape_mesh_start, *shape_mesh_count, *gshape_id;
+    NT_TOPO_TABLE_LIST(NT_TOPO_MEMBER)
     const int* joint_inc;  // [2 nj] inverse of body_joint_list: position of (joint j, side) = code j << 1 | side in the list, -1 (world side)
     // [np][4] (not in the pair-heavy tile): a pair as the contact phases need it -- shape0, shape1 in the narrow phase's type-sorted
     // order (narrow_phase.py:525-528), their bodies (-1 static), bit 30 of the last word: shape0 is the pair's second shape
@@ -225,28 +243,69 @@ struct Topo {
     float* gworld;        // [ng][13] world transform + gap-widened AABB of the global shapes (static: staged once per launch)
     int *hit_count, *hit_list;  // pair-heavy tile only: the environment's compacted candidate list (1 + np ints)
 };
-__host__ __device__ inline int topo_ints(const nt_model& m) {
-    return m.nb + 9 * m.nj + 6 * (m.ns + m.ng) + 2 * m.np + 2 * (m.nb + 1) + 2 * m.nj + 2 * m.np + m.ng +
-           NT_SHAPE_PARAM_FLOATS * m.ng + 13 * m.ng + 2 * m.nj + (m.contact_scratch_in_hbm ? 1 + m.np : 4 * m.np);
-}
-// The block-shared region in the order Ctx lays it out: the tables of Topo up to gshape_id (sources and lengths below), gshape
-// [NT_SHAPE_PARAM_FLOATS ng], gworld [13 ng], joint_inc [2 nj], then pair_desc [4 np] or (pair-heavy tile) hit_count + hit_list
-// [1 + np] -- topo_ints(m) words; the parameter copy of a uniform-parameter tile follows.  The tile image (nt_model.tile_image_words) is this region packed
-// on the host (nt_model_build.hip), which walks the same list: the order is written down here and nowhere else.
-constexpr int NT_TOPO_TABLES = 23;
 struct TopoTables {
     const int32_t* src[NT_TOPO_TABLES];
     int len[NT_TOPO_TABLES];
 };
 __host__ __device__ inline TopoTables topo_tables(const nt_model& m) {
-    const int nsg = m.ns + m.ng;
-    return TopoTables{
-        {m.body_flags, m.joint_type, m.joint_enabled, m.joint_parent, m.joint_child, m.joint_q_start, m.joint_qd_start, m.joint_tq_start,
-         m.joint_lin_count, m.joint_ang_count, m.shape_body, m.shape_type, m.shape_flags, m.shape_group, m.pair_a, m.pair_b,
-         m.body_joint_start, m.body_joint_list, m.body_pair_start, m.body_pair_list, m.shape_mesh_start, m.shape_mesh_count, m.gshape_id},
-        {m.nb, m.nj, m.nj, m.nj, m.nj, m.nj, m.nj, m.nj, m.nj, m.nj, nsg, nsg, nsg, nsg, m.np, m.np,
-         m.nb + 1, 2 * m.nj /* padded by the host */, m.nb + 1, 2 * m.np /* padded */, nsg, nsg, m.ng}};
+    return TopoTables{{NT_TOPO_TABLE_LIST(NT_TOPO_SRC)}, {NT_TOPO_TABLE_LIST(NT_TOPO_LEN)}};
 }
+// word offsets of the parts behind the tables; `tail` is where pair_desc or hit_count / hit_list starts
+struct TopoRegion {
+    int gshape, gworld, joint_inc, tail, total;
+};
+// T's table pointers into the region at `base`; returns the words they take (= topo_region(m).gshape)
+__host__ __device__ inline int topo_bind_tables(Topo& T, const nt_model& m, int* base) {
+    int o = 0;
+    NT_TOPO_TABLE_LIST(NT_TOPO_BIND)
+    return o;
+}
+__host__ __device__ inline TopoRegion topo_region(const nt_model& m) {
+    const int len[NT_TOPO_TABLES] = {NT_TOPO_TABLE_LIST(NT_TOPO_LEN)};
+    TopoRegion r;
+    r.gshape = 0;
+#pragma unroll
+    for (int k = 0; k < NT_TOPO_TABLES; ++k) r.gshape += len[k];
+    r.gworld = r.gshape + NT_SHAPE_PARAM_FLOATS * m.ng;
+    r.joint_inc = r.gworld + 13 * m.ng;
+    r.tail = r.joint_inc + 2 * m.nj;
+    r.total = r.tail + (m.contact_scratch_in_hbm ? 1 + m.np : 4 * m.np);
+    return r;
+}
+#undef NT_TOPO_COUNT
+#undef NT_TOPO_MEMBER
+#undef NT_TOPO_SRC
+#undef NT_TOPO_LEN
+#undef NT_TOPO_BIND
+// topo_region(m).total as a closed form, for the host's sizing code and the tiles of 32 / 64 environments (Ctx::topo_words);
+// pack_tile_image checks the two against each other at model creation
+__host__ __device__ inline int topo_ints(const nt_model& m) {
+    return m.nb + 9 * m.nj + 6 * (m.ns + m.ng) + 2 * m.np + 2 * (m.nb + 1) + 2 * m.nj + 2 * m.np + m.ng +
+           NT_SHAPE_PARAM_FLOATS * m.ng + 13 * m.ng + 2 * m.nj + (m.contact_scratch_in_hbm ? 1 + m.np : 4 * m.np);
+}
+// the four pair_desc words of pair i (m's tables must be readable by the caller: the descriptor's own on the device, host copies on the host)
+__host__ __device__ inline void pair_desc_words(const nt_model& m, const int i, int32_t* w) {
+    int sa = m.pair_a[i], sb = m.pair_b[i], swapped = 0;
+    if (m.shape_type[sa] > m.shape_type[sb]) { const int t_ = sa; sa = sb; sb = t_; swapped = 1; }
+    w[0] = sa; w[1] = sb;
+    w[2] = m.shape_body[sa];
+    w[3] = (m.shape_body[sb] & 0x3fffffff) | (swapped << 30);
+}
+// joint_inc entry of code i = joint << 1 | side: its position among the nlist real entries of body_joint_list (the last match), -1 if none
+__host__ __device__ inline int joint_inc_entry(const int32_t* body_joint_list, const int nlist, const int i) {
+    int at = -1;
+    for (int k = 0; k < nlist; ++k)
+        if (body_joint_list[k] == i) at = k;
+    return at;
+}
+// body parameters as the kernels hold them: the inverse mass / inertia of a kinematic body is zero (solver.py:173-187)
+__host__ __device__ inline float effective_body_param(const int comp, const int body_flags, const float v) {
+    const bool inv_row = comp == BP_INV_MASS || (comp >= BP_INV_INERTIA && comp < BP_INV_INERTIA + 9);
+    return inv_row && (body_flags & BODY_KINEMATIC) ? 0.0f : v;
+}
+// word of the block-shared parameter copy (uniform-parameter tiles) that takes element r = comp * n + s of a [ncomp][n] parameter table
+template <int NC>
+__host__ __device__ inline int uni_word(const Fld<NC> f, const int r, const int n) { return f.off + (r % n) * NC + r / n; }
 // 16 bytes of the tile image (one global_load_dwordx4 per lane)
 struct alignas(16) TileImageQuad {
     int32_t w[4];

@@ -6,7 +6,8 @@
 // and the env-major SoA parameter tables, and places them in HIP device memory (or host memory, for inspection and tests).
 // It is the C restatement of the Python host logic in newton_amd/model.py (EnvTemplate, pack_param_arrays, params_uniform,
 // choose_contact_scratch); tests/test_model_build.py holds the two against each other table by table.
-// On top of the tables it packs the tile image (nt_model.tile_image_words, found at body_flags): the block-shared region of the kernels' LDS tile, word for word (write_tile_image).
+// On top of the tables it packs the tile image (nt_model.tile_image_words, found at body_flags): the block-shared region of the
+// kernels' LDS tile, word for word (pack_tile_image).
 // Host code only: no kernels in this unit.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -21,7 +22,7 @@
 
 namespace {
 
-#include "nt_layout.hpp"  // (the tile's layout: make_layout, topo_ints, topo_tables -- the image below restates none of it)
+#include "nt_layout.hpp"  // (the tile's layout and the description of its block-shared region: the image below restates none of it)
 
 thread_local std::string g_error;
 
@@ -471,71 +472,45 @@ void build(const nt_newton_model& s, nt_model_handle& h) {
     d.tile_image_words = words;
 }
 
-// The tile image: what the Ctx constructor (nt_ctx.hpp) would stage into the block-shared region of a tile, packed once here --
-// the tables of topo_tables(), gshape_param, the gworld gap (the kernels fill it per launch), joint_inc, pair_desc (pair-heavy tile:
-// the hit-list gap), topo_ints() words; then, while params_uniform holds, the parameter copy of a uniform-parameter tile as
-// load_uniform_params lays it out (column 0, effective inverse mass / inertia).  Sized for both parts whatever the flag says now, so
-// that nt_model_refresh_params rewrites it in place.
+// The tile image: the block-shared region of a tile as nt_layout.hpp describes it (NT_TOPO_TABLE_LIST, topo_region), packed once here:
+// the tables, gshape_param, the gworld gap (the kernels fill it per launch), joint_inc, pair_desc (pair-heavy tile: the hit-list gap);
+// then, while params_uniform holds, the parameter copy of a uniform-parameter tile (column 0, effective inverse mass / inertia, words
+// by uni_word).  Sized for both parts whatever the flag says now, so that nt_model_refresh_params rewrites it in place.
 std::vector<int32_t> pack_tile_image(nt_model_handle& h, const Params& P, int& words) {
     const nt_model& d = h.desc;
-    nt_model hd = d;  // the descriptor over the HOST copies of its tables
-    const int32_t** const tabs[NT_TOPO_TABLES] = {
-        &hd.body_flags, &hd.joint_type, &hd.joint_enabled, &hd.joint_parent, &hd.joint_child, &hd.joint_q_start, &hd.joint_qd_start,
-        &hd.joint_tq_start, &hd.joint_lin_count, &hd.joint_ang_count, &hd.shape_body, &hd.shape_type, &hd.shape_flags, &hd.shape_group,
-        &hd.pair_a, &hd.pair_b, &hd.body_joint_start, &hd.body_joint_list, &hd.body_pair_start, &hd.body_pair_list, &hd.shape_mesh_start,
-        &hd.shape_mesh_count, &hd.gshape_id};
-    for (const int32_t** t : tabs) *t = h.host_of(*t).data();
-    const TopoTables tt = topo_tables(hd);
-    const int topo = topo_ints(d);
+    nt_model m = d;  // the descriptor over the HOST copies of its tables
+#define NT_HOST_TABLE(name, len) m.name = h.host_of(m.name).data();
+    NT_TOPO_TABLE_LIST(NT_HOST_TABLE)
+#undef NT_HOST_TABLE
+    const TopoTables tt = topo_tables(m);
+    const TopoRegion tr = topo_region(m);
     const LdsLayout L = make_layout(d, d.contact_scratch_in_hbm != 0, false, true);
-    std::vector<int32_t> img(((size_t)topo + L.uni_floats + 3) / 4 * 4, 0);
+    std::vector<int32_t> img(((size_t)tr.total + L.uni_floats + 3) / 4 * 4, 0);
     int o = 0;
     for (int k = 0; k < NT_TOPO_TABLES; ++k) {
         if (tt.len[k]) memcpy(&img[o], tt.src[k], (size_t)tt.len[k] * 4);
         o += tt.len[k];
     }
-    if (d.ng) memcpy(&img[o], P.gshape.data(), (size_t)NT_SHAPE_PARAM_FLOATS * d.ng * 4);
-    o += NT_SHAPE_PARAM_FLOATS * d.ng;
-    o += 13 * d.ng;  // gworld
-    {  // joint_inc (Ctx::stage_joint_inc): the last match among the list's real entries
-        const int nlist = d.nj > 0 ? hd.body_joint_start[d.nb] : 0;
-        for (int i = 0; i < 2 * d.nj; ++i) {
-            int at = -1;
-            for (int k = 0; k < nlist; ++k)
-                if (hd.body_joint_list[k] == i) at = k;
-            img[o + i] = at;
-        }
-        o += 2 * d.nj;
-    }
-    if (!d.contact_scratch_in_hbm) {  // pair_desc: the type-sorted shapes, their bodies, bit 30: swapped
-        for (int i = 0; i < d.np; ++i) {
-            int sa = hd.pair_a[i], sb = hd.pair_b[i], swapped = 0;
-            if (hd.shape_type[sa] > hd.shape_type[sb]) { std::swap(sa, sb); swapped = 1; }
-            img[o + 4 * i] = sa; img[o + 4 * i + 1] = sb;
-            img[o + 4 * i + 2] = hd.shape_body[sa];
-            img[o + 4 * i + 3] = (hd.shape_body[sb] & 0x3fffffff) | (swapped << 30);
-        }
-        o += 4 * d.np;
-    } else {
-        o += 1 + d.np;  // hit_count + hit_list
-    }
-    if (o != topo) throw Fail{NT_ERR_INVALID_ARG, "tile image: the topology region does not add up to topo_ints"};
-    words = topo;
+    // the walk against the closed form the launch code sizes LDS with, in both tile modes
+    nt_model other = m;
+    other.contact_scratch_in_hbm = !m.contact_scratch_in_hbm;
+    if (o != tr.gshape || tr.total != topo_ints(m) || topo_region(other).total != topo_ints(other))
+        throw Fail{NT_ERR_INVALID_ARG, "tile image: the walked region does not add up to topo_ints"};
+    if (d.ng) memcpy(&img[tr.gshape], P.gshape.data(), (size_t)NT_SHAPE_PARAM_FLOATS * d.ng * 4);
+    const int nlist = d.nj > 0 ? m.body_joint_start[d.nb] : 0;
+    for (int i = 0; i < 2 * d.nj; ++i) img[tr.joint_inc + i] = joint_inc_entry(m.body_joint_list, nlist, i);
+    if (!d.contact_scratch_in_hbm)
+        for (int i = 0; i < d.np; ++i) pair_desc_words(m, i, &img[tr.tail + 4 * i]);
+    words = tr.total;
     if (P.uniform) {
         const size_t ES = d.env_stride;
-        float* up = reinterpret_cast<float*>(&img[topo]);
-        for (int b = 0; b < d.nb; ++b)
-            for (int c = 0; c < NT_BODY_PARAM_FLOATS; ++c) {
-                const bool inv_row = c == BP_INV_MASS || (c >= BP_INV_INERTIA && c < BP_INV_INERTIA + 9);
-                up[L.bp.off + b * NC_BP + c] = inv_row && (hd.body_flags[b] & BODY_KINEMATIC) ? 0.0f : P.body[((size_t)c * d.nb + b) * ES];
-            }
-        for (int j = 0; j < d.nj; ++j)
-            for (int c = 0; c < NT_JOINT_PARAM_FLOATS; ++c) up[L.jp.off + j * NC_JP + c] = P.joint[((size_t)c * d.nj + j) * ES];
-        for (int k = 0; k < d.nd; ++k)
-            for (int c = 0; c < NT_DOF_PARAM_FLOATS; ++c) up[L.dp.off + k * NC_DP + c] = P.dof[((size_t)c * d.nd + k) * ES];
-        for (int s = 0; s < d.ns; ++s)
-            for (int c = 0; c < NT_SHAPE_PARAM_FLOATS; ++c) up[L.sp.off + s * NC_SP + c] = P.shape[((size_t)c * d.ns + s) * ES];
-        words = topo + L.uni_floats;
+        float* up = reinterpret_cast<float*>(&img[tr.total]);
+        for (int r = 0; r < NT_BODY_PARAM_FLOATS * d.nb; ++r)
+            up[uni_word(L.bp, r, d.nb)] = effective_body_param(r / d.nb, m.body_flags[r % d.nb], P.body[r * ES]);
+        for (int r = 0; r < NT_JOINT_PARAM_FLOATS * d.nj; ++r) up[uni_word(L.jp, r, d.nj)] = P.joint[r * ES];
+        for (int r = 0; r < NT_DOF_PARAM_FLOATS * d.nd; ++r) up[uni_word(L.dp, r, d.nd)] = P.dof[r * ES];
+        for (int r = 0; r < NT_SHAPE_PARAM_FLOATS * d.ns; ++r) up[uni_word(L.sp, r, d.ns)] = P.shape[r * ES];
+        words = tr.total + L.uni_floats;
     }
     return img;
 }

@@ -51,7 +51,7 @@ NT_DI void seed_body_forces(const Ctx<EPB>& c, bool forces_are_zero) {
     if (forces_are_zero) {  // (rows, not elements: the pad row is cleared with the rest)
         for (int r = c.slot; r < 7 * nb; r += c.nslot) c.lds[(c.L.bf.off + r) * Ctx<EPB>::N + c.e] = 0.0f;
     } else {
-        stage_rows(c, c.L.bf, c.a.s_in.body_f, 6, nb);
+        stage_rows(c, c.L.bf, c.a.s_in.body_f, 6, nb, c.slot);
     }
 }
 template <int EPB>

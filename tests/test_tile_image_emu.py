@@ -321,6 +321,30 @@ def test_collide_and_step_call_by_call(H, quadrupeds40):
     assert got[3][:40].min() > 0
 
 
+def test_tables_longer_than_the_workgroup(H):
+    """The pair-heavy scene: pair tables, incidence list and image are longer than one trip of the workgroup (at most 384 lanes), so
+    the table-by-table staging runs its tail loops and the image copy its trips beyond the two issued at once.  One collide launch."""
+    from scenes import hull_bin_scene
+
+    em = _emu_model(H, hull_bin_scene(1, 40))
+    try:
+        assert em.desc.contact_scratch_in_hbm == 1
+        assert em.t.np > 384 and em.desc.tile_image_words > 2 * 384 * 4
+
+        def collide(image):
+            a, ct = H.EmuState(em), H.EmuContacts(em)
+            with _env(NT_XPBD_CFG=None, NT_TILE_IMAGE=None if image else "0"):
+                H.collide(em, a, ct)
+            live = np.broadcast_to((ct.shape0 >= 0)[None, ...], ct.data.shape)  # (a dead slot's record is whatever was there)
+            return ct.shape0.copy(), ct.env_count.copy(), np.where(live, ct.data.view(np.int32), 0)
+
+        got = collide(True)
+        _same(got, collide(False))
+        assert got[1][0] > 0
+    finally:
+        em.image_handle.close()
+
+
 def test_semi_implicit_and_featherstone_rollouts(H):
     from newton_amd import _lib as L
 
