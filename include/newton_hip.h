@@ -242,7 +242,10 @@ typedef struct {
     /* SolverFeatherstone(update_mass_matrix_interval = k) (solver_featherstone.py:141,767): substep s of a call rebuilds
      * P / H and refactorises when mass_matrix_cache is NULL, force_update != 0 (first substep only: the reference's
      * _mass_matrix_dirty), or (step_index + s) % k == 0; the Cholesky factor ([nd * max_art_dofs][ES], env-major) is stored
-     * to / reloaded from mass_matrix_cache in between.  Zero-initialised fields = rebuild every step (k = 1). */
+     * to / reloaded from mass_matrix_cache in between.  Zero-initialised fields = rebuild every step (k = 1).
+     * Rows of that buffer a launch touches, columns < env_count only: dense_mass_matrix = 1 all nd * max_art_dofs; tree mode the
+     * packed lower triangles of the articulations one behind the other, sum_k n_k (n_k + 1) / 2 <= nd * max_art_dofs rows
+     * (n_k = dofs of articulation k).  The two modes lay the rows out differently: a cache is not carried across a mode switch. */
     int32_t update_mass_matrix_interval;
     int32_t step_index;
     int32_t force_update;

@@ -1304,6 +1304,9 @@ NT_DI void fs_substep(const Ctx<EPB>& c, const FsCtx<EPB>& f, const FsLayout& F,
     const bool update_mass = fs_update_mass(c, substep);
     float* cache = a.fp.mass_matrix_cache;
     const bool tree = a.fp.dense_mass_matrix == 0 && f.tree_ok;  // block-uniform
+    // rows of F.H that the cache keeps: dense nd W; tree the packed lower triangles of the articulations, one behind the other
+    // (sum of n_k (n_k + 1) / 2 = the offset behind the last dof's diagonal entry, <= nd W: the cache is [nd W][ES] in both modes)
+    const int cache_rows = tree ? f.rowbase[m.nd - 1] + m.nd : m.nd * W;
     // eval_rigid_tau, part 2: one lane per dof, in the barrier interval of the mass-matrix build (tau is first read by the solve)
     if (c.valid && !NT_SKIP(8))
         for (int d = c.slot; d < m.nd; d += c.nslot) fs_tau_dof_item(f, d);
@@ -1325,7 +1328,7 @@ NT_DI void fs_substep(const Ctx<EPB>& c, const FsCtx<EPB>& f, const FsLayout& F,
         if (c.valid && !NT_SKIP(32))
             for (int i = c.slot; i < m.nd * W; i += c.nslot) fs_H_item(f, i);
     } else if (c.valid) {  // the factor of the last rebuild
-        for (int r = c.slot; r < (tree ? fs_tree_nnz_bound(m) : m.nd * W); r += c.nslot) f.f(F.H, r) = cache[(size_t)r * c.ES + c.env];
+        for (int r = c.slot; r < cache_rows; r += c.nslot) f.f(F.H, r) = cache[(size_t)r * c.ES + c.env];
     }
     __syncthreads();
     NT_TICK(17);
@@ -1338,7 +1341,7 @@ NT_DI void fs_substep(const Ctx<EPB>& c, const FsCtx<EPB>& f, const FsLayout& F,
     }
     __syncthreads();
     if (update_mass && cache && a.fp.update_mass_matrix_interval > 1 && c.valid)
-        for (int r = c.slot; r < (tree ? fs_tree_nnz_bound(m) : m.nd * W); r += c.nslot) cache[(size_t)r * c.ES + c.env] = f.f(F.H, r);
+        for (int r = c.slot; r < cache_rows; r += c.nslot) cache[(size_t)r * c.ES + c.env] = f.f(F.H, r);
     NT_TICK(18);
     // integrate_generalized_joints
     const bool desc_free = f.any_descendant_free();  // block-uniform

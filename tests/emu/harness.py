@@ -212,9 +212,20 @@ def semi_implicit_step(em, s_in, s_out, control, contacts, dt, epb=0, angular_da
                                       C.byref(dct) if dct is not None else None, float(dt), epb, None), "nt_semi_implicit_step")
 
 
-def featherstone_step(em, s_in, s_out, control, contacts, dt, epb=0, angular_damping=0.05, friction_smoothing=1.0, dense=False):
+def _featherstone_params(angular_damping, friction_smoothing, dense, update_mass_matrix_interval, step_index, force_update, cache):
+    """cache: the caller's factor buffer ([nd * max_art_dofs][env_stride] float32 by contract; the kernel gets its base pointer)."""
     p = L.nt_featherstone_params(angular_damping, friction_smoothing)
     p.dense_mass_matrix = int(dense)
+    if cache is not None:
+        assert cache.dtype == np.float32 and cache.flags["C_CONTIGUOUS"]
+        p.update_mass_matrix_interval, p.step_index = int(update_mass_matrix_interval), int(step_index)
+        p.force_update, p.mass_matrix_cache = int(force_update), _ptr(cache)
+    return p
+
+
+def featherstone_step(em, s_in, s_out, control, contacts, dt, epb=0, angular_damping=0.05, friction_smoothing=1.0, dense=False,
+                      update_mass_matrix_interval=1, step_index=0, force_update=False, cache=None):
+    p = _featherstone_params(angular_damping, friction_smoothing, dense, update_mass_matrix_interval, step_index, force_update, cache)
     di, do_, dc = s_in.desc(), s_out.desc(), control.desc()
     dct = contacts.desc() if contacts is not None else None
     check(lib().nt_featherstone_step(C.byref(em.desc), C.byref(p), C.byref(di), C.byref(do_), C.byref(dc),
@@ -222,9 +233,9 @@ def featherstone_step(em, s_in, s_out, control, contacts, dt, epb=0, angular_dam
 
 
 def featherstone_rollout(em, s0, s1, control, contacts, dt, substeps, epb=0, angular_damping=0.05, friction_smoothing=1.0,
-                         dense=False):
-    p, cp = L.nt_featherstone_params(angular_damping, friction_smoothing), L.nt_collide_params(0, epb)
-    p.dense_mass_matrix = int(dense)
+                         dense=False, update_mass_matrix_interval=1, step_index=0, force_update=False, cache=None):
+    p = _featherstone_params(angular_damping, friction_smoothing, dense, update_mass_matrix_interval, step_index, force_update, cache)
+    cp = L.nt_collide_params(0, epb)
     d0, d1, dc, dct = s0.desc(), s1.desc(), control.desc(), contacts.desc()
     check(lib().nt_featherstone_rollout(C.byref(em.desc), C.byref(p), C.byref(cp), C.byref(d0), C.byref(d1), C.byref(dc),
                                         C.byref(dct), float(dt), int(substeps), None), "nt_featherstone_rollout")

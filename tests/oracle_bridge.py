@@ -292,14 +292,15 @@ class Oracle:
                                     C.byref(contacts.struct) if contacts is not None else None, C.c_float(dt))
 
     def featherstone_step(self, s_in: OracleState, s_out: OracleState, control, contacts, dt, angular_damping=0.05,
-                          friction_smoothing=1.0, update_mass_matrix_interval=1):
+                          friction_smoothing=1.0, update_mass_matrix_interval=1, force_update=False):
         """SolverFeatherstone.step: advances joint_q/joint_qd and rebuilds body_q/body_qd (s_in.body_q is refreshed by FK).
-        update_mass_matrix_interval > 1: this facade keeps the step counter and the factor cache like the reference solver."""
+        update_mass_matrix_interval > 1: this facade keeps the step counter and the factor cache like the reference solver;
+        force_update: the reference's _mass_matrix_dirty -- this step rebuilds whatever the counter says, and the counter advances."""
         p = o_featherstone_params(angular_damping, friction_smoothing, 1, None)
         if update_mass_matrix_interval > 1:
             if not hasattr(self, "_fs_cache"):
                 self._fs_cache, self._fs_step = np.zeros(max(self.model.joint_dof_count, 1) ** 2, dtype=np.float32), 0
-            p.update_mass_matrix = 1 if self._fs_step % update_mass_matrix_interval == 0 else 0
+            p.update_mass_matrix = 1 if force_update or self._fs_step % update_mass_matrix_interval == 0 else 0
             p.mass_matrix_cache = _fp(self._fs_cache)
             self._fs_step += 1
         si, so = s_in.struct, s_out.struct

@@ -217,6 +217,64 @@ def pendulum_scene(world_count: int, device=None, seed: int | None = None):
     return model
 
 
+def multi_articulation_scene(world_count: int, device=None, seed: int = 7, variant: str = "mixed"):
+    """Three articulations per world (na = 3, max_art_dofs = 6 < nd) in free flight over a ground plane, spinning and with
+    anisotropic inertia, so that a mass-matrix factor kept from an earlier step differs measurably from a fresh one (cubes at rest
+    cannot tell the two apart).  Every body starts at z >= 1 and more than 0.5 m from its neighbours: no contact in a dozen steps.
+      "mixed": a free box (half extents 0.2 / 0.08 / 0.05), a two-link revolute-Y chain hung from the world, a free capsule --
+               dofs 6 / 2 / 6, nd = 14;
+      "free3": three free boxes of different sizes and proportions -- dofs 6 / 6 / 6, nd = 18.
+    Per world (seeded): random unit quaternions for the free roots, chain angles U(-0.8, 0.8), joint_qd ~ N(0, 1.5)."""
+    from newton_amd import _np_math as nm
+
+    env = nt.ModelBuilder()
+    if variant == "mixed":
+        b = env.add_body(xform=[0.0, 0.0, 1.5, 0.0, 0.0, 0.0, 1.0])
+        env.add_shape_box(b, hx=0.2, hy=0.08, hz=0.05)
+        hx = 0.25
+        l0 = env.add_link()
+        env.add_shape_box(l0, hx=hx, hy=0.06, hz=0.04)
+        l1 = env.add_link()
+        env.add_shape_box(l1, hx=hx, hy=0.04, hz=0.05)
+        rot = nm.quat_from_axis_angle([0.0, 0.0, 1.0], -np.pi * 0.5)
+        j0 = env.add_joint_revolute(-1, l0, axis=[0.0, 1.0, 0.0], parent_xform=nm.transform([-1.2, 0.0, 2.6], rot),
+                                    child_xform=nm.transform([-hx, 0.0, 0.0]))
+        j1 = env.add_joint_revolute(l0, l1, axis=[0.0, 1.0, 0.0], parent_xform=nm.transform([hx, 0.0, 0.0]),
+                                    child_xform=nm.transform([-hx, 0.0, 0.0]))
+        env.add_articulation([j0, j1])
+        b = env.add_body(xform=[1.0, 1.0, 1.6, 0.0, 0.0, 0.0, 1.0])
+        env.add_shape_capsule(b, radius=0.05, half_height=0.2)
+    elif variant == "free3":
+        for k, (hx, hy, hz) in enumerate(((0.2, 0.08, 0.05), (0.06, 0.3, 0.1), (0.07, 0.12, 0.25))):
+            b = env.add_body(xform=[1.2 * (k - 1), 0.0, 1.5 + 0.1 * k, 0.0, 0.0, 0.0, 1.0])
+            env.add_shape_box(b, hx=hx, hy=hy, hz=hz)
+    else:
+        raise ValueError(variant)
+    # the bodies never meet: only the (analytic) ground-plane pairs stay, so the model keeps the tiles of the all-analytic scenes
+    for a in range(env.shape_count):
+        for b2 in range(a + 1, env.shape_count):
+            env.add_shape_collision_filter_pair(a, b2)
+    scene = nt.ModelBuilder()
+    scene.replicate(env, world_count)
+    scene.add_ground_plane()
+    model = scene.finalize(device=device)
+    rng = np.random.default_rng(seed)
+    E, t = world_count, model.env
+    jq = model.joint_q.reshape(E, -1).copy()
+    for j in range(t.nj):
+        qs = int(t.joint_q_start[j])
+        if int(t.joint_type[j]) == nt.JointType.FREE:
+            q = rng.normal(size=(E, 4))
+            jq[:, qs + 3:qs + 7] = q / np.linalg.norm(q, axis=1, keepdims=True)
+        else:
+            jq[:, qs] = rng.uniform(-0.8, 0.8, size=E)
+    model.joint_q = jq.reshape(-1).astype(np.float32)
+    model.joint_qd = rng.normal(0.0, 1.5, size=model.joint_qd.shape).astype(np.float32)
+    bq, bqd = nt.articulation.eval_fk_numpy(model, model.joint_q, model.joint_qd)
+    model.body_q, model.body_qd = bq, bqd
+    return model
+
+
 def joint_zoo_scene(world_count: int, device=None, seed: int | None = 0, free_root: bool = False):
     """One articulation per env exercising every supported joint type:
     (world | FREE) -> revolute -> prismatic -> ball -> fixed -> D6(linear x, angular z), plus limits, drives and damping."""
