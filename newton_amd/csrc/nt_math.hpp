@@ -213,11 +213,15 @@ NT_DI quat quat_from_matrix(const mat33& m) {
 
 // newton.math.quat_decompose (math/spatial.py:150-176): wrapped XYZ Euler coordinates (a0, a1, a2) with
 // q = Rx(a0) Ry(a1) Rz(a2), the intrinsic chain compute_3d_rotational_dofs composes (the reference: wp.quat_to_euler(q, 2, 1, 0))
+// Near the gimbal lock the branch is chosen by cos(a1) = |(R12, R22)|, which keeps its absolute accuracy there, not by sin(a1) = R02:
+// the fp32 matrix of a pose AT the lock has R02 up to 3 ulp below 1 while R12, R22, R01, R00 are rounding noise, and the regular
+// branch would return a0 and a2 from that noise.  Below cos(a1) = 4e-4 the third angle is folded into the first (composed rotation
+// off by at most 2 cos(a1)); above it noise / cos(a1) stays below 1e-3 (tests/test_d6_angular_emu.py, tests/test_gpu_d6_angular.py).
 NT_DI vec3 quat_decompose(quat q) {
     mat33 R = quat_to_matrix(q);
-    float sb = clampf(R.m02, -1.0f, 1.0f);
-    float a, b = asinf(sb), c;
-    if (fabsf(sb) < 0.9999999f) {
+    float sb = R.m02, cb = sqrtf(R.m12 * R.m12 + R.m22 * R.m22);
+    float a, b = atan2f(sb, cb), c;
+    if (cb >= 4.0e-4f) {
         a = atan2f(-R.m12, R.m22);
         c = atan2f(-R.m01, R.m00);
     } else {

@@ -156,11 +156,16 @@ inline mat33 quat_to_matrix(quat q) {
 // q = Rx(a0) * Ry(a1) * Rz(a2), i.e. the intrinsic X-Y'-Z'' chain that compute_3d_rotational_dofs composes.  The reference gets
 // them from wp.quat_to_euler(q, 2, 1, 0) (un-vendored Warp builtin, Bernardes & Viollet 2022); restated here through the
 // rotation matrix, same angles up to rounding away from the gimbal lock |a1| = pi/2.
+// Near the lock the branch is chosen by cos(a1) = |(R12, R22)|, which keeps its absolute accuracy there, not by sin(a1) = R02: the
+// fp32 matrix of a pose AT the lock has R02 up to 3 ulp below 1 (a1 off by sqrt(2 * 3 ulp) = 6e-4 through asin) while R12, R22, R01,
+// R00 are rounding noise -- a test of R02 against 1 - 1 ulp took the regular branch there and returned a0 and a2 from that noise (the
+// composed rotation off by |a0 + a2|, 0.9 rad in tests/test_d6_angular_emu.py).  Below cos(a1) = 4e-4 the third angle is folded
+// into the first (the composed rotation is then off by at most 2 cos(a1) = 8e-4); above it the noise / cos(a1) stays below 1e-3.
 inline vec3 quat_decompose(quat q) {
     mat33 R = quat_to_matrix(q);
-    float sb = clampf(R(0, 2), -1.0f, 1.0f);
-    float a, b = std::asin(sb), c;
-    if (std::fabs(sb) < 0.9999999f) {
+    float sb = R(0, 2), cb = std::sqrt(R(1, 2) * R(1, 2) + R(2, 2) * R(2, 2));
+    float a, b = std::atan2(sb, cb), c;
+    if (cb >= 4.0e-4f) {
         a = std::atan2(-R(1, 2), R(2, 2));
         c = std::atan2(-R(0, 1), R(0, 0));
     } else {

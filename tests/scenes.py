@@ -336,6 +336,67 @@ def joint_zoo_scene(world_count: int, device=None, seed: int | None = 0, free_ro
     return model
 
 
+def d6_angular_scene(world_count: int, device=None, seed: int | None = 0, free_root: bool = False):
+    """D6 joints with two and three angular axes in one chain (the joint zoo has none):
+    (world revolute | FREE) -> link0 -D6(angular x, y: one with limits, one driven)-> link1
+    -D6(linear x + angular y, z, armature, velocity target)-> link2 -D6(angular x, z, y, rotated anchors)-> link3.
+    Collision is off; per-world random joint_q in +-0.5 and joint_qd, posed through eval_fk_numpy."""
+    from newton_amd import _np_math as nm
+
+    env = nt.ModelBuilder()
+    cfg = nt.ModelBuilder.ShapeConfig(has_shape_collision=False)
+    links = []
+    for k in range(4):
+        b = env.add_link(xform=[0.3 * k, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0])
+        env.add_shape_box(b, hx=0.12, hy=0.05 + 0.01 * k, hz=0.04, cfg=cfg)
+        links.append(b)
+    X = lambda p, q=(0.0, 0.0, 0.0, 1.0): nm.transform(p, q)  # noqa: E731
+    D = nt.ModelBuilder.JointDofConfig
+    joints = []
+    if free_root:
+        joints.append(env.add_joint_free(links[0]))
+    else:
+        joints.append(env.add_joint_revolute(-1, links[0], axis=[0.0, 1.0, 0.0], parent_xform=X([0.0, 0.0, 1.0]),
+                                             child_xform=X([-0.15, 0.0, 0.0]), target_ke=50.0, target_kd=2.0))
+    joints.append(env.add_joint_d6(links[0], links[1], parent_xform=X([0.15, 0.0, 0.0]), child_xform=X([-0.15, 0.0, 0.0]),
+                                   # (soft limits: joint_q in +-0.5 starts beyond them in about half of the worlds, and the default
+                                   # limit_ke = 1e4 on these 2 kg links would throw link1 to 100 rad/s within one step of 1 ms)
+                                   angular_axes=[D(axis=0, limit_lower=-0.2, limit_upper=0.3, limit_ke=50.0, limit_kd=1.0, armature=0.01),
+                                                 D(axis=1, target_ke=40.0, target_kd=1.0, target_pos=0.1, armature=0.01)]))
+    joints.append(env.add_joint_d6(links[1], links[2], parent_xform=X([0.15, 0.0, 0.0]), child_xform=X([-0.15, 0.0, 0.0]),
+                                   linear_axes=[D(axis=0, limit_lower=-0.05, limit_upper=0.05, armature=0.01)],
+                                   angular_axes=[D(axis=1, target_kd=0.5, target_vel=0.4, armature=0.02),
+                                                 D(axis=2, target_ke=20.0, target_kd=0.5, armature=0.02)]))
+    joints.append(env.add_joint_d6(links[2], links[3], parent_xform=X([0.15, 0.0, 0.0], nm.quat_rpy(0.2, -0.1, 0.3)),
+                                   child_xform=X([-0.15, 0.0, 0.0], nm.quat_rpy(-0.1, 0.15, 0.05)),
+                                   angular_axes=[D(axis=a, target_ke=15.0, target_kd=0.3, armature=0.01) for a in (0, 2, 1)]))
+    env.add_articulation(joints)
+    scene = nt.ModelBuilder()
+    scene.replicate(env, world_count)
+    model = scene.finalize(device=device)
+    if seed is not None:
+        rng = np.random.default_rng(seed)
+        E = world_count
+        jq = model.joint_q.reshape(E, -1).copy()
+        t = model.env
+        for j in range(t.nj):
+            qs = int(t.joint_q_start[j])
+            if int(t.joint_type[j]) == nt.JointType.FREE:
+                q = rng.normal(size=(E, 4)) * 0.3 + np.array([0, 0, 0, 1.0])
+                jq[:, qs + 3:qs + 7] = q / np.linalg.norm(q, axis=1, keepdims=True)
+                jq[:, qs:qs + 3] += rng.normal(0, 0.05, size=(E, 3))
+            else:
+                n = int(t.joint_lin_count[j] + t.joint_ang_count[j])
+                jq[:, qs:qs + n] = rng.uniform(-0.5, 0.5, size=(E, n))
+                if int(t.joint_lin_count[j]):
+                    jq[:, qs] *= 0.1  # (the linear coordinate: within its +-0.05 m limits)
+        model.joint_q = jq.reshape(-1).astype(np.float32)
+        model.joint_qd = rng.normal(0.0, 0.5, size=model.joint_qd.shape).astype(np.float32)
+        bq, bqd = nt.articulation.eval_fk_numpy(model, model.joint_q, model.joint_qd)
+        model.body_q, model.body_qd = bq, bqd
+    return model
+
+
 def free_child_scene(world_count: int, device=None, seed: int | None = 0, free_root: bool = False):
     """FREE and DISTANCE joints below the articulation root (SolverFeatherstone keeps them in internal parent-origin
     coordinates and re-integrates the child pose at the end of the step, solver_featherstone.py:229-265,1006-1046):

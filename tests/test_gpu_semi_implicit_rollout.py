@@ -45,7 +45,14 @@ def _box_stack(n):
     return model, None, 1e-4
 
 
-SCENES = {"pendulum": _pendulum, "quadruped": _quadruped, "box_stack": _box_stack}
+def _d6_angular(n):
+    from scenes import d6_angular_scene
+
+    model = d6_angular_scene(n, device="cuda:0", seed=13, free_root=True)  # D6 joints with two and three angular axes
+    return model, np.random.default_rng(4).normal(0, 0.5, size=model.joint_dof_count).astype(np.float32), 1e-4
+
+
+SCENES = {"pendulum": _pendulum, "quadruped": _quadruped, "box_stack": _box_stack, "d6_angular": _d6_angular}
 
 
 def _control(model, jf):
@@ -91,7 +98,7 @@ def _check_rollout_equals_loop(model, jf, dt, substeps, min_contacts=0):
 @pytest.mark.parametrize("scene", sorted(SCENES))
 def test_rollout_equals_loop_bitwise(scene, substeps):
     model, jf, dt = SCENES[scene](37)
-    _check_rollout_equals_loop(model, jf, dt, substeps, min_contacts=0 if scene == "pendulum" else 37)
+    _check_rollout_equals_loop(model, jf, dt, substeps, min_contacts=0 if scene in ("pendulum", "d6_angular") else 37)
 
 
 def test_rollout_equals_loop_bitwise_at_full_size():

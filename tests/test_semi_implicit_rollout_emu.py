@@ -75,7 +75,14 @@ def _box_stack():
     return model, None, 1e-4
 
 
-SCENES = {"pendulum": _pendulum, "quadruped": _quadruped, "box_stack": _box_stack}
+def _d6_angular():
+    from scenes import d6_angular_scene
+
+    model = d6_angular_scene(N_WORLDS, seed=13, free_root=True)  # D6 joints with two and three angular axes
+    return model, np.random.default_rng(4).normal(0, 0.5, size=model.joint_dof_count).astype(np.float32), 1e-4
+
+
+SCENES = {"pendulum": _pendulum, "quadruped": _quadruped, "box_stack": _box_stack, "d6_angular": _d6_angular}
 
 
 @pytest.mark.parametrize("epb", [1, 8])
@@ -113,7 +120,7 @@ def test_rollout_equals_loop_bitwise(H, scene, substeps, epb):
     # 2. body_f of both states zero, the Contacts are the last collide's
     assert not r0.aos("body_f").any() and not r1.aos("body_f").any()
     n = int(lexp["count"][0])
-    assert int(rexp["count"][0]) == n and (scene == "pendulum" or n > 0)
+    assert int(rexp["count"][0]) == n and (scene in ("pendulum", "d6_angular") or n > 0)
     for k, v in lexp.items():
         assert np.array_equal(rexp[k], v), k
     assert np.array_equal(rct.env_count[:E], lct.env_count[:E])
