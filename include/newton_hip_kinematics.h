@@ -100,6 +100,50 @@ nt_status nt_eval_mass_matrix(const nt_model* m, const nt_state* in, float* H, f
 nt_status nt_eval_mass_matrix_tile(const nt_model* m, const nt_state* in, float* H, float* body_I_s, const uint8_t* art_mask,
                                    int32_t envs_per_block, void* stream);
 
+/* Inverse dynamics: joint torques for a given joint acceleration, and with it the bias forces h(q, q') = C(q, q') q' + g(q)
+ * (joint_qdd NULL) -- the capability of the tensor APIs' generalized gravity / Coriolis-and-centrifugal force getters, in the
+ * convention of nt_eval_jacobian / nt_eval_mass_matrix above:
+ *   nt_eval_inverse_dynamics   (newton_amd.eval_inverse_dynamics; the reference has no single call for it)
+ * With S_d the column of dof d (joint_S_s), J_l the 6 x D block of link l, I_l its world-frame spatial inertia (body_I_s), q' the public
+ * joint_qd (a FREE / DISTANCE joint carries the COM velocity), q'' = joint_qdd and g this world's row of nt_model.gravity:
+ *   v_l = J_l q'                        (origin-referenced world twist, linear first)
+ *   a_l = J_l q'' + J'_l q'             J'_l q' = sum over the dofs d on l's root path of S'_d q'_d
+ *   f_l = I_l a_l + v_l x* (I_l v_l) - (m_l g, c_l x m_l g)
+ *   tau = sum_l J_l^T f_l               tau . q' is power; tau(q'') - tau(0) = H q'' with nt_eval_mass_matrix's H
+ * S'_d is the time derivative of the closed form of S_d above along the motion q'.  A linear direction a carried by a frame of angular
+ * velocity w_F gives (w_F x a, 0); an axis w through a pivot p gives (p' x w + p x (w_F x w), w_F x w).  The frames:
+ *   PRISMATIC, REVOLUTE, BALL   axes carried by the parent link; the pivot is the parent anchor and moves with the parent
+ *   FREE, DISTANCE              axes carried by the parent anchor frame; the pivot is the child's COM and moves with the child
+ *   D6                          linear axes carried by the parent; angular axis k by the parent plus the joint's earlier angular dofs
+ *                               (w_F = w_parent + sum_{m<k} a_m q'_m); the pivot p_j moves with the parent plus the joint's linear dofs
+ * The rigid-body term only, like H: no armature, no joint limits, no drives, no friction.  This is not the bias force
+ * nt_featherstone_step forms (that one is in the solver's internal FREE-joint convention); for chains of 1-dof joints the two coincide.
+ *
+ * flags: NT_ID_GRAVITY includes g(q); NT_ID_VELOCITY includes the terms in joint_qd (Coriolis / centrifugal), clear = joint_qd is taken
+ * as 0.  Both clear and joint_qdd NULL: tau = 0 exactly.
+ * joint_qdd and tau: the PUBLIC layout [env_count * na][D], D = nt_model.max_art_dofs -- the rows and columns of H.  The padding of tau
+ * (an articulation narrower than D) is written as zero by every call.  joint_qdd is read through the pointer at launch time: an in-place
+ * update followed by a graph replay takes effect.
+ * Inputs read: in->body_q, in->joint_q (as nt_eval_jacobian) and in->joint_qd; in->body_qd is not read.  After a maximal-coordinate
+ * step call nt_eval_ik first.  Multi-axis D6 joints as for nt_eval_ik (the caller vouches).  The joints of an articulation must come
+ * parent before child (what the model builder makes).
+ * One launch of eval_inverse_dynamics_kernel on eval_mass_matrix_kernel's tile: one lane per (environment, link) accumulates v_l and
+ * a_l over the dofs on the link's root path in ascending dof order and forms f_l; one lane per (environment, dof) sums S_d . f_l over
+ * the links below it in ascending joint order.  Gravity enters as the root acceleration -g, which is the definition above term by
+ * term.  Twists, accelerations and wrenches are referenced to the articulation's root link position (tau does not depend on the point;
+ * world coordinates of a far-away world would cost the m |c|^2 and c x f terms their digits).  No atomics, a fixed summation order,
+ * IEEE arithmetic: every tile computes the same bits, replicated worlds in equal states give equal bits.
+ * art_mask as for nt_eval_jacobian, with the same contiguity precondition: the slices of unselected articulations are neither computed
+ * nor written.  No scratch state, no allocation, no synchronisation; recordable by nt_graph_capture_begin / _end.  Errors: those of
+ * nt_eval_mass_matrix (null m / in / body_q / joint_q / joint_qd / tau NT_ERR_INVALID_ARG), and NT_ERR_INVALID_ARG for unknown flag
+ * bits.  The _tile form names the tile as nt_eval_ik_tile does. */
+#define NT_ID_GRAVITY  1   /* include g(q) */
+#define NT_ID_VELOCITY 2   /* include the terms in joint_qd (Coriolis / centrifugal); clear = treat joint_qd as 0 */
+nt_status nt_eval_inverse_dynamics(const nt_model* m, const nt_state* in, const float* joint_qdd /* [env_count*na][D] or NULL = 0 */,
+                                   int32_t flags, float* tau /* [env_count*na][D] */, const uint8_t* art_mask, void* stream);
+nt_status nt_eval_inverse_dynamics_tile(const nt_model* m, const nt_state* in, const float* joint_qdd, int32_t flags, float* tau,
+                                        const uint8_t* art_mask, int32_t envs_per_block, void* stream);
+
 /* Batched inverse kinematics (the capability of the reference's newton.ik.IKSolver: position / rotation / joint-limit objectives,
  * Levenberg-Marquardt):
  *   nt_ik_solve           <- newton.ik.IKSolver.step(joint_q_in, joint_q_out, iterations, step_size)     newton/_src/sim/ik/

@@ -926,3 +926,260 @@ def _eval_jm_groups(model, state, which, out, aux, art_sel):
 
     groups.run(go)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# eval_inverse_dynamics
+# ---------------------------------------------------------------------------------------------------------------------------------
+NT_ID_GRAVITY, NT_ID_VELOCITY = 1, 2  # include/newton_hip_kinematics.h
+
+
+def _parent_first(model, what):
+    """The walk down a link's root path takes the dofs in ascending order: a joint's ancestor must come before it."""
+    t = model.env
+    ok = getattr(t, "_parent_first", None)
+    if ok is None:
+        _, anc = _joint_ancestors(t)
+        ok = bool(np.all(anc < np.arange(t.nj)))
+        try:
+            t._parent_first = ok
+        except AttributeError:
+            pass
+    if not ok:
+        raise NotImplementedError(f"{what}: the joints of an articulation must come parent before child (unsupported)")
+
+
+def _joint_pivots_numpy(model, body_q, joint_q):
+    """[E, nj, 3] in float64: the point the angular columns of each joint pass through (_motion_subspace_numpy's)."""
+    t = model.env
+    E, nb, nj = t.env_count, t.nb, t.nj
+    bq = np.asarray(body_q, dtype=np.float64).reshape(E, nb, 7)
+    jq = np.asarray(joint_q, dtype=np.float64).reshape(E, t.nc)
+    com = np.asarray(model.body_com, dtype=np.float64).reshape(E, nb, 3)
+    X_p = np.asarray(model.joint_X_p, dtype=np.float64).reshape(E, nj, 7)
+    axis_all = np.asarray(model.joint_axis, dtype=np.float64).reshape(E, t.nd, 3)
+    piv = np.zeros((E, nj, 3))
+    for j in range(nj):
+        jt, parent, child = int(t.joint_type[j]), int(t.joint_parent[j]), int(t.joint_child[j])
+        qs, ds, lin = int(t.joint_q_start[j]), int(t.joint_qd_start[j]), int(t.joint_lin_count[j])
+        X_wpj = X_p[:, j] if parent < 0 else _xmul(bq[:, parent], X_p[:, j])
+        if jt in (JointType.FREE, JointType.DISTANCE):
+            piv[:, j] = bq[:, child, :3] + _qrot(bq[:, child, 3:], com[:, child])
+        elif jt == JointType.D6:
+            pos = np.zeros((E, 3))
+            for k in range(lin):
+                pos += axis_all[:, ds + k] * jq[:, qs + k:qs + k + 1]
+            piv[:, j] = X_wpj[:, :3] + _qrot(X_wpj[:, 3:], pos)
+        else:
+            piv[:, j] = X_wpj[:, :3]
+    return piv
+
+
+def _world_gravity(model):
+    """[E, 3] float64: the gravity row of each world (the row of its first body, as the device tables)."""
+    t = model.env
+    g = np.asarray(model.gravity, dtype=np.float64).reshape(-1, 3)
+    world = np.asarray(model.body_world).reshape(t.env_count, t.nb)[:, 0] if t.nb else np.zeros(t.env_count, dtype=np.int64)
+    return g[world]
+
+
+def _split_parts(parts, value, key, width=None):
+    sizes = np.cumsum([getattr(p, key) for p in parts])[:-1]
+    a = np.asarray(value)
+    return np.split(a.reshape(-1) if width is None else a.reshape(-1, width), sizes)
+
+
+def eval_inverse_dynamics_numpy(model, body_q, joint_q, joint_qd, joint_qdd=None, tau=None, gravity=True, velocity_terms=True, art_sel=None):
+    """Host mirror of eval_inverse_dynamics_kernel: tau [articulation_count, D] = sum over links of J_l^T f_l with
+    f_l = I_l a_l + v_l x* (I_l v_l) - (m_l g, c_l x m_l g), in float64 from the definition of include/newton_hip_kinematics.h (about the
+    world origin, link by link; the kernel works about the root link), float32 out.  ``joint_qdd`` [articulation_count, D] or None (zero);
+    the slices of articulations ``art_sel`` leaves out stay untouched."""
+    D = _art_dims(model)[1]
+    A = int(model.articulation_count)
+    tau = _new_or_checked(tau, (A, D), "tau")
+    if joint_qdd is not None:
+        joint_qdd = np.asarray(joint_qdd)
+        if joint_qdd.shape != (A, D):
+            raise ValueError(f"joint_qdd must have shape {(A, D)}")
+    if getattr(model, "is_heterogeneous", False):
+        parts = model.world_groups.parts
+        bqs, jqs = _split_parts(parts, body_q, "body_count", 7), _split_parts(parts, joint_q, "joint_coord_count")
+        jqds = _split_parts(parts, joint_qd, "joint_dof_count")
+        a0 = 0
+        for p, bq, jq, jqd in zip(parts, bqs, jqs, jqds):
+            a1 = a0 + p.articulation_count
+            if p.articulation_count:
+                sel = None if art_sel is None else np.asarray(art_sel, dtype=bool)[a0:a1]
+                Dp = _art_dims(p)[1]
+                tp = np.array(tau[a0:a1, :Dp])
+                eval_inverse_dynamics_numpy(p, bq, jq, jqd, None if joint_qdd is None else joint_qdd[a0:a1, :Dp], tp, gravity,
+                                            velocity_terms, sel)
+                rows = slice(a0, a1) if sel is None else a0 + np.flatnonzero(sel)
+                tau[rows] = 0.0
+                tau[rows, :Dp] = tp if sel is None else tp[sel]
+            a0 = a1
+        return tau
+    t = _articulated(model, "eval_inverse_dynamics")
+    check_ik_supported(model)
+    _parent_first(model, "eval_inverse_dynamics")
+    E, nd = t.env_count, t.nd
+    S = _motion_subspace_numpy(model, body_q, joint_q)
+    I_s = _spatial_inertia_numpy(model, body_q)
+    piv = _joint_pivots_numpy(model, body_q, joint_q)
+    on = _path_matrix(t)
+    dof_joint = np.searchsorted(t.joint_qd_start, np.arange(nd), side="right") - 1 if nd else np.zeros(0, dtype=np.int64)
+    qd = np.asarray(joint_qd, dtype=np.float64).reshape(E, nd) if velocity_terms else np.zeros((E, nd))
+    qdd = np.zeros((E, nd))
+    ranges = _art_ranges(t)
+    if joint_qdd is not None:
+        for k, (_j0, _nja, d0, nda) in enumerate(ranges):
+            qdd[:, d0:d0 + nda] = np.asarray(joint_qdd, dtype=np.float64).reshape(E, t.na, D)[:, k, :nda]
+    g = _world_gravity(model) if gravity else np.zeros((E, 3))
+    sel = np.ones((E, t.na), dtype=bool) if art_sel is None else np.asarray(art_sel, dtype=bool).reshape(E, t.na)
+    tv = tau.reshape(E, t.na, D)
+    for k, (j0, nja, d0, nda) in enumerate(ranges):
+        blk = np.zeros((E, D))
+        for j in range(j0, j0 + nja):
+            # v_l and a_l = J_l qdd + sum S'_d qd_d down the root path (the running twist is the twist of the frame that carries the
+            # next dof's pivot; its angular part the rate of a D6's axis frame, every other joint's axes ride on the parent link)
+            v, w, al, aw, w_parent = (np.zeros((E, 3)) for _ in range(5))
+            for d in range(d0, d0 + nda):
+                jd = int(dof_joint[d])
+                if not on[j, jd]:
+                    continue
+                jt, i = int(t.joint_type[jd]), d - int(t.joint_qd_start[jd])
+                if i == 0:
+                    w_parent = w.copy()
+                angular = (jt in (JointType.REVOLUTE, JointType.BALL) or (jt in (JointType.FREE, JointType.DISTANCE) and i >= 3)
+                           or (jt == JointType.D6 and i >= int(t.joint_lin_count[jd])))
+                sv, sw = S[:, d, :3], S[:, d, 3:]
+                w_frame = w if jt == JointType.D6 else w_parent
+                if angular:
+                    p_dot = v + np.cross(w, piv[:, jd])
+                    dbottom = np.cross(w_frame, sw)
+                    dtop = np.cross(p_dot, sw) + np.cross(piv[:, jd], dbottom)
+                else:
+                    dtop, dbottom = np.cross(w_frame, sv), np.zeros((E, 3))
+                al = al + sv * qdd[:, d:d + 1] + dtop * qd[:, d:d + 1]
+                aw = aw + sw * qdd[:, d:d + 1] + dbottom * qd[:, d:d + 1]
+                v = v + sv * qd[:, d:d + 1]
+                w = w + sw * qd[:, d:d + 1]
+            Il = I_s[:, int(t.joint_child[j])]
+            vl, acc = np.concatenate([v, w], axis=1), np.concatenate([al - g, aw], axis=1)
+            mom = np.einsum("eij,ej->ei", Il, vl)
+            f = np.einsum("eij,ej->ei", Il, acc)
+            f[:, :3] += np.cross(w, mom[:, :3])
+            f[:, 3:] += np.cross(w, mom[:, 3:]) + np.cross(v, mom[:, :3])
+            cols = on[j, dof_joint[d0:d0 + nda]]
+            blk[:, :nda] += np.einsum("edi,ei->ed", S[:, d0:d0 + nda], f) * cols
+        tv[sel[:, k], k] = blk[sel[:, k]].astype(np.float32)
+    return tau
+
+
+def _device_in(model, value, shape, what):
+    """A resident float32 tensor as it is (checked); anything else is uploaded (one allocation and one host-to-device copy)."""
+    import torch  # noqa: PLC0415
+
+    if hasattr(value, "data_ptr"):
+        return _device_out(model, value, shape, what)
+    a = np.ascontiguousarray(value, dtype=np.float32)
+    if a.shape != tuple(shape):
+        raise ValueError(f"{what} must have shape {tuple(shape)}")
+    return torch.from_numpy(a).to(model.device_model().device)
+
+
+def eval_inverse_dynamics(model, state, joint_qdd=None, tau=None, gravity=True, velocity_terms=True, mask=None):
+    """Inverse dynamics in the convention of :func:`eval_jacobian` / :func:`eval_mass_matrix`: the joint torques ``tau``
+    [articulation_count, D] float32 (D = ``model.max_dofs_per_articulation``, the rows of ``H``) that produce the joint acceleration
+    ``joint_qdd`` [articulation_count, D] at the state's ``joint_q`` / ``joint_qd``:
+
+        ``tau = H joint_qdd + h(q, qd)``,  ``h = C(q, qd) qd + g(q)``, the bias forces
+
+    with eval_mass_matrix's ``H`` -- ``torch.bmm(H, joint_qdd[..., None])`` lines up.  ``joint_qdd=None`` is zero: the call returns
+    ``h``; with ``velocity_terms=False`` the generalized gravity forces alone (what holds the robot still), with ``gravity=False`` the
+    Coriolis / centrifugal forces alone; both off and no ``joint_qdd``: exactly zero.  ``tau . joint_qd`` is power with respect to the
+    public ``joint_qd`` (a FREE / DISTANCE joint carries the COM velocity).  The rigid-body term only, like ``H``: no armature, no joint
+    limits, no drives, no friction -- and not the bias force SolverFeatherstone forms internally (its FREE-joint convention differs; for
+    chains of 1-dof joints the two coincide, so ``control.joint_f = h`` cancels gravity and velocity terms there).  The padding of
+    ``tau`` is written as zero on every call; ``mask`` (bool per articulation) leaves the slices of unselected articulations untouched.
+
+    Reads ``state.body_q``, ``state.joint_q`` and ``state.joint_qd``: after a maximal-coordinate step (SolverXPBD, SolverSemiImplicit)
+    call :func:`eval_ik` first.  A ``tau`` left ``None`` is allocated and returned: a torch tensor on a GPU model, a numpy array on a
+    host model.  On a GPU model with ``tau`` (and ``joint_qdd``, if used) supplied as resident float32 tensors and no ``mask`` the call
+    is one kernel launch on the model's stream (nt_eval_inverse_dynamics): no allocation, no synchronisation, it records into
+    ``newton_amd.graph.capture`` -- ``joint_qdd`` is read at launch time, an in-place update followed by a replay takes effect.  A mask
+    uploads its bytes on every call, a ``joint_qdd`` that is not a device tensor is uploaded.  Multi-axis D6 joints as for
+    :func:`eval_ik`."""
+    art_sel = _mask_selection(model, mask, "eval_inverse_dynamics")
+    if getattr(model, "is_heterogeneous", False):
+        return _eval_id_groups(model, state, joint_qdd, tau, gravity, velocity_terms, art_sel)
+    D = _art_dims(model)[1]
+    if not getattr(model, "is_gpu", False):
+        return eval_inverse_dynamics_numpy(model, _host_array(state.body_q), _host_array(state.joint_q), _host_array(state.joint_qd),
+                                           None if joint_qdd is None else _host_array(joint_qdd), tau, gravity, velocity_terms, art_sel)
+    import ctypes as C  # noqa: PLC0415
+
+    from . import _lib  # noqa: PLC0415
+
+    t = _articulated(model, "eval_inverse_dynamics")
+    check_ik_supported(model)
+    _parent_first(model, "eval_inverse_dynamics")
+    dm = model.device_model()
+    shape = (t.env_count * t.na, D)
+    fresh = tau is None
+    tau = _device_out(model, tau, shape, "tau")
+    if joint_qdd is not None:
+        joint_qdd = _device_in(model, joint_qdd, shape, "joint_qdd")
+    if fresh and art_sel is not None:
+        tau.zero_()
+    art_mask = _device_art_mask(model, art_sel, "eval_inverse_dynamics")
+    d = state._desc()
+    flags = (NT_ID_GRAVITY if gravity else 0) | (NT_ID_VELOCITY if velocity_terms else 0)
+    _lib.check(dm.lib.nt_eval_inverse_dynamics(C.byref(dm.desc), C.byref(d), None if joint_qdd is None else joint_qdd.data_ptr(), flags,
+                                               tau.data_ptr(), None if art_mask is None else art_mask.data_ptr(), dm.stream()),
+               "nt_eval_inverse_dynamics")
+    return tau
+
+
+def _eval_id_groups(model, state, joint_qdd, tau, gravity, velocity_terms, art_sel):
+    """Heterogeneous model: one call per world group (_eval_jm_groups' pattern); a group's articulations are a slice of the global
+    [articulation_count, D] arrays, padded to the widest group's D."""
+    groups = model.world_groups
+    parts = groups.parts
+    D = _art_dims(model)[1]
+    A = int(model.articulation_count)
+    if not getattr(model, "is_gpu", False):
+        return eval_inverse_dynamics_numpy(model, _host_array(state.body_q), _host_array(state.joint_q), _host_array(state.joint_qd),
+                                           None if joint_qdd is None else _host_array(joint_qdd), tau, gravity, velocity_terms, art_sel)
+    import torch  # noqa: PLC0415
+
+    dev = parts[0].device_model().device
+    if tau is None:
+        tau = torch.zeros((A, D), dtype=torch.float32, device=dev)
+    elif not (hasattr(tau, "data_ptr") and tau.dtype == torch.float32 and tuple(tau.shape) == (A, D)):
+        raise ValueError(f"tau must be a float32 tensor of shape {(A, D)}")
+    if joint_qdd is not None:
+        if not hasattr(joint_qdd, "data_ptr"):
+            joint_qdd = torch.from_numpy(np.ascontiguousarray(joint_qdd, dtype=np.float32)).to(dev)
+        if joint_qdd.dtype != torch.float32 or tuple(joint_qdd.shape) != (A, D):
+            raise ValueError(f"joint_qdd must be a float32 tensor of shape {(A, D)}")
+    a_edges = np.concatenate([[0], np.cumsum([p.articulation_count for p in parts])])
+
+    def go(i, p):
+        if not p.articulation_count:
+            return
+        a0, a1 = int(a_edges[i]), int(a_edges[i + 1])
+        sel = None if art_sel is None else art_sel[a0:a1]
+        Dp = _art_dims(p)[1]
+        kw = dict(gravity=gravity, velocity_terms=velocity_terms, mask=sel)
+        if Dp == D:  # the group's slice has the global shape: read and written in place
+            eval_inverse_dynamics(p, state.parts[i], None if joint_qdd is None else joint_qdd[a0:a1], tau[a0:a1], **kw)
+            return
+        got = eval_inverse_dynamics(p, state.parts[i], None if joint_qdd is None else joint_qdd[a0:a1, :Dp].contiguous(), None, **kw)
+        rows = torch.arange(a0, a1, device=dev) if sel is None else torch.as_tensor(a0 + np.flatnonzero(sel), device=dev)
+        pick = slice(None) if sel is None else torch.as_tensor(np.flatnonzero(sel), device=dev)
+        tau[rows] = 0.0
+        tau[rows, :Dp] = got[pick]
+
+    groups.run(go)
+    return tau

@@ -1,9 +1,9 @@
 // nt_featherstone.hip -- SolverFeatherstone (step / fused rollout), eval_fk and eval_ik: launch code + C ABI.  The solver's kernels are
 // nt_featherstone_kernels.hpp, their phases nt_featherstone.hpp (namespace ieee); this unit exists so that they are compiled with the
-// default scheduler (see nt_step_preamble.hpp).  eval_ik, eval_jacobian, eval_mass_matrix, ik_solve and frame_sensor (kernels and entry
+// default scheduler (see nt_step_preamble.hpp).  eval_ik, eval_jacobian, eval_mass_matrix, eval_inverse_dynamics, ik_solve and frame_sensor (kernels and entry
 // points, include/newton_hip_kinematics.h) live here whole: the headers the stepping unit shares stay as they are.
 // Launch code: the solver's tile choice is fs_launch (a measured rule of its own); every kinematics entry point -- nt_eval_fk and the
-// four _tile entry points -- chooses its tile and launches through ONE function, kin_launch, below the kernels.
+// five _tile entry points -- chooses its tile and launches through ONE function, kin_launch, below the kernels.
 #include "nt_step_preamble.hpp"
 #ifndef NT_EMULATED_GRID
 #include "../../include/newton_hip_kinematics.h"
@@ -609,6 +609,165 @@ __global__ void __launch_bounds__(256) eval_mass_matrix_kernel(KArgs a, float* H
 }
 
 // ------------------------------------------------------------------------------------------------
+// nt_eval_inverse_dynamics (contract: include/newton_hip_kinematics.h): tau = sum_l J_l^T f_l, f_l = I_l a_l + v_l x* (I_l v_l) with
+// gravity entering as the root acceleration -g.  Tile: eval_jacobian_kernel's (poses, parameters, joint_q, S), then the link inertias
+// [10][nj] (NOT composed), joint_qd [nd], joint_qdd [nd] (gathered from the public layout), the joint pivots [3][nj], the link wrenches
+// [6][nj] and tau (env-major [e][nd], odd stride).  Twists, accelerations and wrenches are spatial (the body-fixed point that passes
+// through the reference point), referenced to the articulation's root link position; tau does not depend on the point.
+// One lane per (environment, link) walks the dofs on the link's root path in ascending order -- the ancestors' dofs come first, the
+// model builder's order -- and carries the running twist: at dof d it IS the twist of the frame that carries d's pivot (the parent
+// link plus the joint's earlier dofs; those act through the pivot or are linear), and its angular part the rate of the frame that
+// carries d's axis for a D6 (parent plus the earlier angular dofs); every other type's axes ride on the parent: the angular rate
+// when the walk entered the joint.  The link's wrench follows in the same lane: v, a and f never leave registers between the two.
+// ------------------------------------------------------------------------------------------------
+struct IdLayout {
+    JmLayout F;
+    int qd, qdd, piv, f, tau, TW;
+};
+__host__ __device__ inline IdLayout id_layout(const nt_model& m, const bool uni) {
+    IdLayout I;
+    I.F = jm_layout(m, uni, false);
+    int o = I.F.rows;
+    I.F.Ic = o; o += 10 * m.nj;
+    I.qd = o; o += m.nd;
+    I.qdd = o; o += m.nd;
+    I.piv = o; o += 3 * m.nj;
+    I.f = o; o += 6 * m.nj;
+    I.TW = m.nd | 1;
+    I.tau = o; o += I.TW;
+    I.F.rows = o;
+    return I;
+}
+
+// the pivot of joint j's angular dofs (jm_S_item's)
+template <int EPB>
+NT_DI vec3 id_pivot(const JmCtx<EPB>& f, int j) {
+    const Ctx<EPB>& c = f.c;
+    const nt_model& m = c.a.m;
+    const int parent = c.T.joint_parent[j], child = c.T.joint_child[j], type = c.T.joint_type[j];
+    if (type == JT_FREE || type == JT_DISTANCE) return xform_point(c.body_q(child), c.com(child));
+    xform X_wpj = c.plxf(c.L.jp, 0, m.nj, j);
+    if (parent >= 0) X_wpj = c.body_q(parent) * X_wpj;
+    if (type != JT_D6) return X_wpj.p;
+    const int ds = c.T.joint_qd_start[j], cs = c.T.joint_q_start[j], lin = c.T.joint_lin_count[j];
+    vec3 pos(0.0f);
+    for (int i = 0; i < lin; ++i) pos += c.dof_axis(ds + i) * f.jq(cs + i);
+    return xform_point(X_wpj, pos);
+}
+
+// tau [env_count * na][D] in the public layout; joint_qdd the same layout or NULL (zero).  art_mask as for eval_ik_kernel.
+template <int EPB>
+__global__ void __launch_bounds__(256) eval_inverse_dynamics_kernel(KArgs a, const float* joint_qdd, int flags, float* tau,
+                                                                    const uint8_t* art_mask) {
+    extern __shared__ __align__(16) float lds[];
+    const nt_model& m = a.m;
+    constexpr int N = Ctx<EPB>::N;
+    const IdLayout I = id_layout(m, Ctx<EPB>::UNI);
+    Ctx<EPB> c(a, lds, I.F.rows);
+    int* extra = c.own_tables(jm_table_ints(m));
+    __syncthreads();
+    jm_build_tables(c, extra);
+    const JmCtx<EPB> f(c, I.F, extra);
+    const int D = m.max_art_dofs;
+    jm_load(c, I.F);
+    const bool with_velocity = (flags & NT_ID_VELOCITY) != 0;
+    if (c.valid) {
+        if (with_velocity) stage_rows(c, I.qd, a.s_in.joint_qd, m.nd);
+        else
+            for (int d = c.slot; d < m.nd; d += c.nslot) lds[(I.qd + d) * N + c.e] = 0.0f;
+    }
+    // joint_qdd: the tile's articulations out of the public layout, consecutive lanes on consecutive dofs
+    for (int t = 0; t < N * m.na; ++t) {
+        const int e = t / m.na, k = t - e * m.na, env = blockIdx.x * N + e;
+        if (env >= m.env_count) break;
+        if (art_mask && !art_mask[(size_t)env * m.na + k]) continue;
+        const int j0 = m.art_start[k], nja = m.art_start[k + 1] - j0;
+        const int d0 = nja > 0 ? c.T.joint_qd_start[j0] : 0, nda = nja > 0 ? f.qd_end(j0 + nja - 1) - d0 : 0;
+        const float* in = joint_qdd ? joint_qdd + (size_t)((size_t)env * m.na + k) * D : nullptr;
+        for (int i = threadIdx.x; i < nda; i += blockDim.x) lds[(I.qdd + d0 + i) * N + e] = in ? in[i] : 0.0f;
+    }
+    __syncthreads();
+    auto selected = [&](int j) { return !art_mask || art_mask[(size_t)c.env * m.na + f.art[j]]; };
+    auto root_pos = [&](int j) { return c.body_q(c.T.joint_child[m.art_start[f.art[j]]]).p; };
+    auto row3 = [&](int off, int j) { return vec3(lds[(off + j) * N + c.e], lds[(off + m.nj + j) * N + c.e], lds[(off + 2 * m.nj + j) * N + c.e]); };
+    auto S_lin = [&](int d) { return vec3(f.S(c.e, 0, d), f.S(c.e, 1, d), f.S(c.e, 2, d)); };
+    auto S_ang = [&](int d) { return vec3(f.S(c.e, 3, d), f.S(c.e, 4, d), f.S(c.e, 5, d)); };
+    // (1) S_d, the link inertias and the pivots, about the root link position
+    if (c.valid) {
+        for (int d = c.slot; d < m.nd; d += c.nslot)
+            if (selected(f.dof_joint[d])) jm_S_item(f, d, root_pos(f.dof_joint[d]));
+        for (int j = c.slot; j < m.nj; j += c.nslot) {
+            if (!selected(j)) continue;
+            jm_inertia_item(f, j, root_pos(j), nullptr);
+            const vec3 p = id_pivot(f, j) - root_pos(j);
+            lds[(I.piv + j) * N + c.e] = p.x; lds[(I.piv + m.nj + j) * N + c.e] = p.y; lds[(I.piv + 2 * m.nj + j) * N + c.e] = p.z;
+        }
+    }
+    __syncthreads();
+    // (2) + (3) per (environment, link): v_l and a_l over the dofs on the root path, then f_l
+    if (c.valid)
+        for (int j = c.slot; j < m.nj; j += c.nslot) {
+            if (!selected(j)) continue;
+            const int d0 = c.T.joint_qd_start[m.art_start[f.art[j]]], d1 = f.qd_end(j);
+            vec3 v, w, al, aw, w_parent;
+            if (flags & NT_ID_GRAVITY) al = -c.gravity();
+            for (int d = d0; d < d1; ++d) {
+                const int jd = f.dof_joint[d];
+                if (!f.on_path(jd, j)) continue;
+                const int ds = c.T.joint_qd_start[jd], type = c.T.joint_type[jd], k = d - ds;
+                if (k == 0) w_parent = w;
+                const bool angular = type == JT_REVOLUTE || type == JT_BALL || ((type == JT_FREE || type == JT_DISTANCE) && k >= 3) ||
+                                     (type == JT_D6 && k >= c.T.joint_lin_count[jd]);
+                const vec3 sv = S_lin(d), sw = S_ang(d), w_frame = type == JT_D6 ? w : w_parent;
+                const float qd = lds[(I.qd + d) * N + c.e], qdd = lds[(I.qdd + d) * N + c.e];
+                vec3 dtop, dbottom;
+                if (angular) {
+                    const vec3 r = row3(I.piv, jd), p_dot = v + cross(w, r);
+                    dbottom = cross(w_frame, sw);
+                    dtop = cross(p_dot, sw) + cross(r, dbottom);
+                } else {
+                    dtop = cross(w_frame, sv);
+                }
+                al += sv * qdd + dtop * qd;
+                aw += sw * qdd + dbottom * qd;
+                v += sv * qd;
+                w += sw * qd;
+            }
+            const float mass = f.Ic(0, j);
+            const vec3 hm(f.Ic(1, j), f.Ic(2, j), f.Ic(3, j));
+            const float xx = f.Ic(4, j), xy = f.Ic(5, j), xz = f.Ic(6, j), yy = f.Ic(7, j), yz = f.Ic(8, j), zz = f.Ic(9, j);
+            auto rot = [&](vec3 u) { return vec3(xx * u.x + xy * u.y + xz * u.z, xy * u.x + yy * u.y + yz * u.z, xz * u.x + yz * u.y + zz * u.z); };
+            const vec3 p_lin = v * mass + cross(w, hm), p_ang = cross(hm, v) + rot(w);  // I v
+            const vec3 f_lin = (al * mass + cross(aw, hm)) + cross(w, p_lin);
+            const vec3 f_ang = (cross(hm, al) + rot(aw)) + (cross(w, p_ang) + cross(v, p_lin));
+            lds[(I.f + j) * N + c.e] = f_lin.x; lds[(I.f + m.nj + j) * N + c.e] = f_lin.y; lds[(I.f + 2 * m.nj + j) * N + c.e] = f_lin.z;
+            lds[(I.f + 3 * m.nj + j) * N + c.e] = f_ang.x; lds[(I.f + 4 * m.nj + j) * N + c.e] = f_ang.y; lds[(I.f + 5 * m.nj + j) * N + c.e] = f_ang.z;
+        }
+    __syncthreads();
+    // (4) per (environment, dof): S_d . f_l over the links whose root path holds the dof, in ascending joint order
+    if (c.valid)
+        for (int d = c.slot; d < m.nd; d += c.nslot) {
+            const int jd = f.dof_joint[d];
+            if (!selected(jd)) continue;
+            const vec3 sv = S_lin(d), sw = S_ang(d);
+            float acc = 0.0f;
+            for (int l = jd; l < m.art_start[f.art[jd] + 1]; ++l)
+                if (f.on_path(jd, l)) acc += dot(sv, row3(I.f, l)) + dot(sw, row3(I.f + 3 * m.nj, l));
+            lds[I.tau * N + c.e * I.TW + d] = acc;
+        }
+    __syncthreads();
+    for (int t = 0; t < N * m.na; ++t) {
+        const int e = t / m.na, k = t - e * m.na, env = blockIdx.x * N + e;
+        if (env >= m.env_count) break;
+        if (art_mask && !art_mask[(size_t)env * m.na + k]) continue;
+        const int j0 = m.art_start[k], nja = m.art_start[k + 1] - j0;
+        const int d0 = nja > 0 ? c.T.joint_qd_start[j0] : 0, nda = nja > 0 ? f.qd_end(j0 + nja - 1) - d0 : 0;
+        float* out = tau + (size_t)((size_t)env * m.na + k) * D;
+        for (int i = threadIdx.x; i < D; i += blockDim.x) out[i] = i < nda ? lds[I.tau * N + e * I.TW + d0 + i] : 0.0f;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // nt_ik_solve (newton.ik.IKSolver.step; contract: include/newton_hip_kinematics.h): batched Levenberg-Marquardt IK, one problem per
 // environment, all iterations in one launch.  Tile: eval_jacobian_kernel's (poses, parameters, joint_q, S), then the candidate's
 // joint_q' [nc] and poses [7 nb], the residual blocks of the accepted point and of the candidate (position: residual + world point, 6
@@ -983,7 +1142,7 @@ __global__ void __launch_bounds__(256) ik_solve_kernel(KArgs a, nt_ik_problem P,
 
 // ------------------------------------------------------------------------------------------------
 // kin_launch: the tile rule and the launch of every kinematics entry point (nt_eval_fk, nt_eval_ik_tile, nt_eval_jacobian_tile,
-// nt_eval_mass_matrix_tile, nt_ik_solve_tile).  envs_per_block 0: on replicated worlds (nt_model.params_uniform, UNI_OK) the
+// nt_eval_mass_matrix_tile, nt_eval_inverse_dynamics_tile, nt_ik_solve_tile).  envs_per_block 0: on replicated worlds (nt_model.params_uniform, UNI_OK) the
 // uniform-parameter tile of 16 -- ONE block-shared parameter copy, the parameters are four fifths of what the per-environment tile of
 // eval_ik reads -- if it fits the LDS, otherwise the widest per-environment-parameter tile of 16 / 8 / 4 / 1 that fits.  A named width:
 // that per-environment-parameter tile, if it is one of 1 / 4 / 8 / 16 and fits.  Nothing chosen: NT_ERR_UNSUPPORTED, nothing launched.
@@ -1037,6 +1196,29 @@ static nt_status jm_launch(const nt_model* m, const nt_state* in, float* out, fl
         [&](auto T, int epb, size_t lds_bytes) {
             if constexpr (MASS) return launch_tile(eval_mass_matrix_kernel<T>, a, epb, lds_bytes, stream, out, aux, art_mask);
             else return launch_tile(eval_jacobian_kernel<T>, a, epb, lds_bytes, stream, out, aux, art_mask);
+        });
+#endif
+}
+
+// nt_eval_inverse_dynamics_tile: argument checks and what it brings to kin_launch
+static nt_status id_launch(const nt_model* m, const nt_state* in, const float* joint_qdd, int32_t flags, float* tau, const uint8_t* art_mask,
+                           int32_t envs_per_block, hipStream_t stream) {
+    if (!model_ok(m) || !in || !in->body_q || !in->joint_q || !in->joint_qd || !tau) return NT_ERR_INVALID_ARG;
+    if (flags & ~(NT_ID_GRAVITY | NT_ID_VELOCITY)) return NT_ERR_INVALID_ARG;
+    if (m->nj <= 0 || m->na <= 0 || !m->art_start || m->max_art_dofs < 0) return NT_ERR_UNSUPPORTED;
+#ifdef NT_DEV_FAST
+    return NT_ERR_UNSUPPORTED;
+#else
+    if (m->max_art_dofs == 0) return NT_OK;  // (no dofs: tau has no entries)
+    KArgs a = {};
+    a.m = *m;
+    a.s_in = *in;
+    // slot-lanes: one per dof / joint / body; the gather of joint_qdd and the streaming phase run workgroup-wide
+    return kin_launch<true>(
+        m, a, envs_per_block, (size_t)topo_ints(*m) + jm_table_ints(*m), imax(imax(m->nb, m->nj), m->nd),
+        [&](bool uni) { return id_layout(*m, uni).F.rows; },
+        [&](auto T, int epb, size_t lds_bytes) {
+            return launch_tile(eval_inverse_dynamics_kernel<T>, a, epb, lds_bytes, stream, joint_qdd, (int)flags, tau, art_mask);
         });
 #endif
 }
@@ -1238,6 +1420,17 @@ nt_status nt_eval_mass_matrix_tile(const nt_model* m, const nt_state* in, float*
 
 nt_status nt_eval_mass_matrix(const nt_model* m, const nt_state* in, float* H, float* body_I_s, const uint8_t* art_mask, void* stream) {
     return nt_eval_mass_matrix_tile(m, in, H, body_I_s, art_mask, 0, stream);
+}
+
+// envs_per_block: the tile, by kin_launch's rule (id_launch)
+nt_status nt_eval_inverse_dynamics_tile(const nt_model* m, const nt_state* in, const float* joint_qdd, int32_t flags, float* tau,
+                                        const uint8_t* art_mask, int32_t envs_per_block, void* stream) {
+    return id_launch(m, in, joint_qdd, flags, tau, art_mask, envs_per_block, (hipStream_t)stream);
+}
+
+nt_status nt_eval_inverse_dynamics(const nt_model* m, const nt_state* in, const float* joint_qdd, int32_t flags, float* tau,
+                                   const uint8_t* art_mask, void* stream) {
+    return nt_eval_inverse_dynamics_tile(m, in, joint_qdd, flags, tau, art_mask, 0, stream);
 }
 
 // envs_per_block: the tile, by kin_launch's rule

@@ -1,14 +1,16 @@
 #!/usr/bin/env python
-"""MEASUREMENT TOOL -- nt_eval_jacobian and nt_eval_mass_matrix beside nt_eval_fk and nt_eval_ik on the same model, same process.
+"""MEASUREMENT TOOL -- nt_eval_jacobian, nt_eval_mass_matrix and nt_eval_inverse_dynamics beside nt_eval_fk and nt_eval_ik on the same
+model, same process.
 
     python tools/eval_jacobian_timing.py [--worlds 4096] [--calls 40] [--repeats 7] [--warmup 20] [--peak-gbs X] [--out FILE]
 
 Quadruped scene, outputs in caller tensors.  One HIP event pair around a batch of `--calls` back-to-back launches of one kernel gives a
 per-call time; the kernels take turns batch by batch, `--repeats` (>= 5) batches each; the median and the spread (min .. max) of the
-batches are reported.  Beside each call stand the bytes it must write (J: worlds * 6 L * D * 4; H: worlds * D * D * 4) and read
-(body_q, joint_q), the time those bytes take at the streaming peak (`--peak-gbs`: what `bench.py --full` prints for this box; default:
-a device-to-device copy measured here, read + write counted) and the ratio of the measured time to that floor.  Prints ONE JSON line
-and writes it to --out (default profiles/eval_jacobian_timing.json)."""
+batches are reported.  Beside each call stand the bytes it must write (J: worlds * 6 L * D * 4; H: worlds * D * D * 4; tau:
+worlds * D * 4) and read (body_q, joint_q; inverse dynamics: joint_qd and joint_qdd too), the time those bytes take at the streaming
+peak (`--peak-gbs`: what `bench.py --full` prints for this box; default: a device-to-device copy measured here, read + write counted)
+and the ratio of the measured time to that floor.  Prints ONE JSON line and writes it to --out (default
+profiles/eval_jacobian_timing.json; the run with the inverse-dynamics row is profiles/eval_inverse_dynamics_timing.json)."""
 import argparse
 import ctypes as C
 import json
@@ -63,16 +65,21 @@ def measure(worlds, calls, repeats, warmup, peak_gbs):
     L, D = model.max_joints_per_articulation, model.max_dofs_per_articulation
     J = torch.zeros((worlds * t.na, 6 * L, D), dtype=torch.float32, device="cuda:0")
     H = torch.zeros((worlds * t.na, D, D), dtype=torch.float32, device="cuda:0")
+    tau = torch.zeros((worlds * t.na, D), dtype=torch.float32, device="cuda:0")
+    qdd = torch.from_numpy(rng.uniform(-5.0, 5.0, size=(worlds * t.na, D)).astype(np.float32)).to("cuda:0")
     m, s, st = C.byref(dm.desc), C.byref(d), dm.stream()
     legs = {
         "eval_fk": lambda: _lib.check(lib.nt_eval_fk(m, src_q.data_ptr(), src_qd.data_ptr(), s, st), "nt_eval_fk"),
         "eval_ik": lambda: _lib.check(lib.nt_eval_ik(m, s, out_q.data_ptr(), out_qd.data_ptr(), None, st), "nt_eval_ik"),
         "eval_jacobian": lambda: _lib.check(lib.nt_eval_jacobian(m, s, J.data_ptr(), None, None, st), "nt_eval_jacobian"),
         "eval_mass_matrix": lambda: _lib.check(lib.nt_eval_mass_matrix(m, s, H.data_ptr(), None, None, st), "nt_eval_mass_matrix"),
+        "eval_inverse_dynamics": lambda: _lib.check(lib.nt_eval_inverse_dynamics(m, s, qdd.data_ptr(), 3, tau.data_ptr(), None, st),
+                                                    "nt_eval_inverse_dynamics"),
     }
     state_bytes = worlds * 4 * (7 * t.nb + t.nc)
     traffic = {"eval_fk": (worlds * 4 * (t.nc + t.nd), worlds * 52 * t.nb), "eval_ik": (worlds * 52 * t.nb, worlds * 4 * (t.nc + t.nd)),
-               "eval_jacobian": (state_bytes, J.numel() * 4), "eval_mass_matrix": (state_bytes, H.numel() * 4)}
+               "eval_jacobian": (state_bytes, J.numel() * 4), "eval_mass_matrix": (state_bytes, H.numel() * 4),
+               "eval_inverse_dynamics": (state_bytes + worlds * 4 * t.nd + qdd.numel() * 4, tau.numel() * 4)}
     for _ in range(warmup):
         for f in legs.values():
             f()
