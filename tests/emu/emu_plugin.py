@@ -90,6 +90,7 @@ torch.cuda._newton_emulated = True  # tests that only make sense on the device (
 torch.cuda.current_stream = lambda device=None: _Stream()
 torch.cuda.synchronize = lambda device=None: None
 torch.cuda.set_device = lambda device: None
+torch.cuda.is_current_stream_capturing = lambda: False  # (Contacts.prepare_rollout asks before it allocates)
 
 
 class _DeviceCtx:  # `with torch.cuda.device(d):` -- one (emulated) device, nothing to switch
