@@ -468,6 +468,16 @@ NT_DI void contact_export_item_lds(const Ctx<EPB>& c, const int slot) {
         ct.shape1[gi] = -1;
     }
 }
+// The Contacts output of an LDS-record rollout, called once behind the substep loop: the stores then have no barrier (and its
+// vmcnt(0) wait) of the solve behind them.  What it reads is the last substep's and still intact there: L.cr is written by the record
+// lanes alone, L.pm and the live count L.lc by the pair lanes alone, and none of the three is overlaid by the scratch union.
+template <int EPB>
+NT_DI void export_lds_contacts(const Ctx<EPB>& c) {
+    if (!c.valid) return;
+    const nt_model& m = c.a.m;
+    for (int s = c.slot; s < m.np * m.cpp; s += c.nslot) contact_export_item_lds(c, s);
+    if (c.slot == c.nslot - 1) c.a.ct.env_count[c.env] = *reinterpret_cast<const int*>(&c.l(c.L.lc, 0, 1, 0));  // per-env totals: an API-boundary output
+}
 // second stage, analytic pairs only: contact slot (p, k) <- the pair's k-th admitted candidate
 template <int EPB>
 NT_DI void contact_write_item(const Ctx<EPB>& c, const int slot) {

@@ -294,7 +294,18 @@ struct Ctx {
         for (int i = threadIdx.x; i < 2 * a.m.nj; i += blockDim.x) inv[i] = joint_inc_entry(T.body_joint_list, nlist, i);
     }
     NT_DI xform body_q(int b) const { return lxf(L.bq, 0, a.m.nb, b); }
-    NT_DI xform body_q_in(int b) const { return lxf(Fld<7>{pose_in_off}, 0, a.m.nb, b); }
+    // the step's incoming pose of body b.  NT_SPEC: the rotation from the snapshot rows, the origin from L.bq -- an apply phase follows
+    // (verified by the launch code), so inside a step the origins (rows 0..2) are written by the step's last apply alone, and the
+    // snapshot holds rows 3..6 only (xpbd_integrate_item<EPB, true> fills them)
+    NT_DI xform body_q_in(int b) const {
+        if constexpr (SPEC) {
+            const int nb = a.m.nb;
+            const Fld<7> in{pose_in_off};  // (L.xiq on this instance)
+            return xform(lv3(L.bq, 0, nb, b), quat(l(in, 3, nb, b), l(in, 4, nb, b), l(in, 5, nb, b), l(in, 6, nb, b)));
+        } else {
+            return lxf(Fld<7>{pose_in_off}, 0, a.m.nb, b);
+        }
+    }
     NT_DI quat body_rot(int b) const {
         const int nb = a.m.nb;
         return quat(l(L.bq, 3, nb, b), l(L.bq, 4, nb, b), l(L.bq, 5, nb, b), l(L.bq, 6, nb, b));

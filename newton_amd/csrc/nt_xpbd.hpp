@@ -198,8 +198,11 @@ NT_DI int body_lane_split(const Ctx<EPB>& c) {  // S0 if the linear lanes fit be
     return c.lane_split && S0 + c.a.m.nb <= c.nslot ? S0 : 0;
 }
 // integrate_bodies (solver.py:63-170) of SolverXPBD.  need_p: no apply phase follows in this step -- rebuild the body origin here
-// (both halves on one lane).
-template <int EPB>
+// (both halves on one lane).  SNAP (a fact of the call site: the fused substep that runs this item beside the pair phase, analytic
+// instances, need_p == false): the angular lane leaves the incoming rotation r0 in rows 3..6 of L.xiq before it overwrites L.bq --
+// the pose snapshot the contact writer converts into (Ctx::body_q_in), kinematic bodies included.  Every other caller (step kernels,
+// pair-heavy tile, integrate in an interval of its own) never touches L.xiq: its layout may not have those rows.
+template <int EPB, bool SNAP = false>
 NT_DI void xpbd_integrate_item(const Ctx<EPB>& c, const int b, const bool do_lin, const bool do_ang, const bool need_p) {
     const nt_model& m = c.a.m;
     const int nb = m.nb, nj = m.nj;
@@ -220,6 +223,13 @@ NT_DI void xpbd_integrate_item(const Ctx<EPB>& c, const int b, const bool do_lin
             else t0 -= t;
         }
     }
+    quat r0;
+    if constexpr (SNAP) {
+        if (do_ang) {
+            r0 = c.body_rot(b);
+            c.l(c.L.xiq, 3, nb, b) = r0.x; c.l(c.L.xiq, 4, nb, b) = r0.y; c.l(c.L.xiq, 5, nb, b) = r0.z; c.l(c.L.xiq, 6, nb, b) = r0.w;
+        }
+    }
     if (c.T.body_flags[b] & BODY_KINEMATIC) return;  // pass through unchanged
     const float dt = c.a.dt;
     vec3 x1;
@@ -233,7 +243,7 @@ NT_DI void xpbd_integrate_item(const Ctx<EPB>& c, const int b, const bool do_lin
         c.st_lv3(c.L.bd, 0, nb, b, x1);
     }
     if (do_ang) {
-        const quat r0 = c.body_rot(b);
+        if constexpr (!SNAP) r0 = c.body_rot(b);
         const vec3 w0 = c.body_w(b);
         const mat33 inertia = c.inertia(b), inv_inertia = c.inv_inertia(b);
         const vec3 wb = quat_rotate_inv(r0, w0);
@@ -711,7 +721,7 @@ NT_DI void phase_contacts(const Ctx<EPB>& c) {
 // (it holds q1) also rebuilds the body origin p and the entry-form world COM, the linear lane leaves the COM alone.
 constexpr int NT_APPLY_SLOTS = 5;   // contact slots of a pair fetched together (cpp <= 5)
 constexpr int NT_APPLY_JOINTS = 4;  // incident joints fetched together; longer lists finish in a loop
-template <int EPB, bool FROM_CONTACTS, class CW = CwLds, bool FUSED = false, bool ROWS = !FUSED>
+template <int EPB, bool FROM_CONTACTS, class CW = CwLds, bool FUSED = false, bool ROWS = !FUSED, bool DEAD_W = false>
 NT_DI void apply_item(const Ctx<EPB>& c, const int b, const bool do_lin, const bool do_ang, const bool last) {
     const nt_model& m = c.a.m;
     const int nb = m.nb;
@@ -840,7 +850,12 @@ NT_DI void apply_item(const Ctx<EPB>& c, const int b, const bool do_lin, const b
         if (xlength(w1) < 1e-4f) w1 = vec3(0.0f);
         c.l(c.L.bq, 3, nb, b) = q1.x; c.l(c.L.bq, 4, nb, b) = q1.y; c.l(c.L.bq, 5, nb, b) = q1.z; c.l(c.L.bq, 6, nb, b) = q1.w;
         c.st_lv3(c.L.bqd, 3, nb, b, w1);
-        c.update_body_w(b, q1);
+        // The step's last apply leaves W alone.  Its readers are Ctx::w_tile in the contact solve and the two joint items; the passes
+        // that may still follow in this step read none of it (restitution_item and restitution_apply_item take the body-frame
+        // c.inv_inertia, velocity-from-delta the poses, report_parent_f the joint accumulators), and before the next step's solve
+        // integrate_bodies rebuilds W from its own r1 for every body that reaches this line (a kernel entry: phase_body_derived).
+        // W is never stored.  Kinematic and zero-mass bodies returned above and keep what those two wrote.
+        if (!(DEAD_W && last)) c.update_body_w(b, q1);
     }
     if (do_lin) {
         vec3 v1 = c.body_v(b) + dp;
@@ -854,15 +869,15 @@ NT_DI void apply_item(const Ctx<EPB>& c, const int b, const bool do_lin, const b
         c.update_world_com(b, X);
     }
 }
-template <int EPB, bool FROM_CONTACTS, class CW = CwLds, bool FUSED = false, bool ROWS = !FUSED>
+template <int EPB, bool FROM_CONTACTS, class CW = CwLds, bool FUSED = false, bool ROWS = !FUSED, bool DEAD_W = false>
 NT_DI void phase_apply(const Ctx<EPB>& c, const bool last) {
     if (!c.valid) return;
     const int nb = c.a.m.nb, S0 = body_lane_split(c);
     if (Ctx<EPB>::SPEC || S0) {
-        if (c.slot < nb) apply_item<EPB, FROM_CONTACTS, CW, FUSED, ROWS>(c, c.slot, false, true, last);
-        else if (c.slot >= S0 && c.slot < S0 + nb) apply_item<EPB, FROM_CONTACTS, CW, FUSED, ROWS>(c, c.slot - S0, true, false, last);
+        if (c.slot < nb) apply_item<EPB, FROM_CONTACTS, CW, FUSED, ROWS, DEAD_W>(c, c.slot, false, true, last);
+        else if (c.slot >= S0 && c.slot < S0 + nb) apply_item<EPB, FROM_CONTACTS, CW, FUSED, ROWS, DEAD_W>(c, c.slot - S0, true, false, last);
     } else {
-        for (int b = c.tslot; b < nb; b += c.nslot) apply_item<EPB, FROM_CONTACTS, CW, FUSED, ROWS>(c, b, true, true, last);
+        for (int b = c.tslot; b < nb; b += c.nslot) apply_item<EPB, FROM_CONTACTS, CW, FUSED, ROWS, DEAD_W>(c, b, true, true, last);
     }
 }
 
@@ -1523,6 +1538,10 @@ NT_DI void do_xpbd_step(const Ctx<EPB>& c, bool forces_are_zero) {
     const bool has_contacts = SPEC || c.a.has_contacts != 0, has_joints = SPEC || m.nj > 0;
     if (!PROLOGUE_DONE && (restitution || vel_from_delta) && c.valid)  // body_q_init / body_qd_init: the state the step starts from
         for (int r = c.slot; r < 14 * m.nb; r += c.nslot) c.lds[(c.L.xiq.off + r) * Ctx<EPB>::N + c.e] = c.lds[(c.L.bq.off + r) * Ctx<EPB>::N + c.e];
+    // the step's last apply skips the W rebuild (apply_item) in the step kernels, the pair-heavy rollout and NT_SPEC; the generic
+    // staged rollouts keep it: without it the rescheduled substep loop of the tile of 32 was measured 1 % slower
+    // (profiles/substep_chain_ab.txt)
+    constexpr bool DEAD_W = SPEC || !PROLOGUE_DONE;
     const bool rep_joints = !FUSED && c.a.rep.joint_impulse != nullptr;
     const bool rep_contacts = !FUSED && c.a.rep.contact_impulse != nullptr && c.a.has_contacts;
     if (!PROLOGUE_DONE && !NT_SKIP(2)) {
@@ -1546,7 +1565,7 @@ NT_DI void do_xpbd_step(const Ctx<EPB>& c, bool forces_are_zero) {
                 report_contact_iteration<EPB, CW>(c, it == 0);
                 if constexpr (!FUSED) report_flat_rows_iteration<EPB, CW>(c, it == 0);
             }
-            if (!NT_SKIP(16)) phase_apply<EPB, true, CW, FUSED, ROWS>(c, last_it && !has_joints);
+            if (!NT_SKIP(16)) phase_apply<EPB, true, CW, FUSED, ROWS, DEAD_W>(c, last_it && !has_joints);
             __syncthreads();
             NT_TICK(6);
         }
@@ -1555,7 +1574,7 @@ NT_DI void do_xpbd_step(const Ctx<EPB>& c, bool forces_are_zero) {
             __syncthreads();
             NT_TICK(7);
             if (rep_joints) report_joint_iteration(c);
-            if (!NT_SKIP(16)) phase_apply<EPB, false>(c, last_it);
+            if (!NT_SKIP(16)) phase_apply<EPB, false, CwLds, false, true, DEAD_W>(c, last_it);
             __syncthreads();
             NT_TICK(8);
         }

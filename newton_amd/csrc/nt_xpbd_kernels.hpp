@@ -63,14 +63,22 @@ NT_DI void do_fused_substep(const Ctx<EPB>& c, const fused::Ctx<EPB>& cf, bool l
     // -- interval 1: shapes (slots [0, ns)) || joint forces (slots [S0, S0 + nj), S0 on a wave boundary) + body_f_tmp = 0
     const bool compact = pairs_compacted(c);
     // integrate_bodies beside the pair phase (its 13 lanes on the waves the 13 pair lanes leave idle; the pair phase is the longer of
-    // the two): the contact writer then converts into the snapshot of the incoming poses (c.pose_in_off) taken in interval 1
+    // the two): the contact writer then converts into the snapshot of the incoming poses (c.pose_in_off, Ctx::body_q_in)
     const int I0 = SPEC ? c.R.I0 : ((m.np + spw - 1) / spw) * spw;
     const bool overlap = SPEC || c.pose_in_off != c.L.bq.off;
     const bool need_p = !SPEC && !fused::xpbd_applies_follow(c.a);  // integrate_bodies rebuilds the body origins itself
+    // NT_SPEC takes the snapshot without a copy pass: the origins stay in L.bq until the step's last apply, and the integrate lane
+    // stores the rotation it has loaded into L.xiq before overwriting it (xpbd_integrate_item<EPB, true>).  The copy (7 rows per
+    // body at the head of interval 1) stays on every generic instance.  It is needed by (a) the convex instances -- their pair lanes
+    // call write_contact_slot -> body_q_in inside interval 2, the interval in which integrate writes those rows, (b) need_p, where
+    // integrate rewrites the origins as well, and (c) restitution / velocity-from-delta, which keep all 14 rows as the pre-step
+    // state; the generic analytic instances could drop it but were measured slower without it (the tile of 32, which never
+    // overlaps, lost 1 % to the rescheduled loop: profiles/substep_chain_ab.txt).
+    const bool snapshot_copy = !SPEC && (restitution || overlap);
     if (c.valid) {
         if (compact && c.slot == 0) *reinterpret_cast<int*>(&c.l(c.L.hc, 0, 1, 0)) = 0;
         if (c.lds_records && c.slot == 0) *reinterpret_cast<int*>(&c.l(c.L.lc, 0, 1, 0)) = 0;
-        if (restitution || overlap)
+        if (snapshot_copy)
             for (int r = c.slot; r < (restitution ? 14 : 7) * m.nb; r += c.nslot) c.lds[(c.L.xiq.off + r) * Ctx<EPB>::N + c.e] = c.lds[(c.L.bq.off + r) * Ctx<EPB>::N + c.e];
         if (!NT_SKIP(2)) fused::seed_body_forces(cf, true);
         const int S0 = SPEC ? c.R.S0 : ((m.ns + spw - 1) / spw) * spw;
@@ -91,7 +99,7 @@ NT_DI void do_fused_substep(const Ctx<EPB>& c, const fused::Ctx<EPB>& cf, bool l
             __syncthreads();
             phase_pair_narrow_staged<EPB, CVX>(c);
         } else if (overlap && c.slot >= I0) {
-            if (c.valid && c.slot < I0 + m.nb && !NT_SKIP(2)) fused::xpbd_integrate_item(cf, c.slot - I0, true, true, need_p);
+            if (c.valid && c.slot < I0 + m.nb && !NT_SKIP(2)) fused::xpbd_integrate_item<EPB, SPEC>(cf, c.slot - I0, true, true, need_p);
         } else {
             phase_pair_eval<EPB, CVX>(c);
         }
@@ -105,7 +113,9 @@ NT_DI void do_fused_substep(const Ctx<EPB>& c, const fused::Ctx<EPB>& cf, bool l
         for (int i = c.slot; i < total; i += c.nslot) contact_record_item_lds(c, *reinterpret_cast<const int*>(&c.l(c.L.lt, 0, 1, i)));
         if (c.slot == c.nslot - 1) {
             c.l(c.L.px, 0, 1, m.np) = (float)total;
-            if (last_substep) c.a.ct.env_count[c.env] = total;  // per-env totals: an API-boundary output
+            if constexpr (!SPEC) {  // (NT_SPEC: export_lds_contacts, behind the substep loop)
+                if (last_substep) c.a.ct.env_count[c.env] = total;  // per-env totals: an API-boundary output
+            }
         }
     } else if (!NT_SKIP(1) && c.valid) {
         const int nas = m.np_analytic * m.cpp;
@@ -126,8 +136,10 @@ NT_DI void do_fused_substep(const Ctx<EPB>& c, const fused::Ctx<EPB>& cf, bool l
         phase_pair_prefix_scan(c, c.L.sx.off, last_substep, false);
         __syncthreads();
     }
-    if (c.lds_records && last_substep && c.valid)  // the launch's Contacts output (reads L.cr / L.pm only: no barrier needed behind it)
-        for (int s = c.slot; s < m.np * m.cpp; s += c.nslot) contact_export_item_lds(c, s);
+    if constexpr (!SPEC) {  // (NT_SPEC: export_lds_contacts, behind the substep loop)
+        if (c.lds_records && last_substep && c.valid)  // the launch's Contacts output (reads L.cr / L.pm only: no barrier needed behind it)
+            for (int s = c.slot; s < m.np * m.cpp; s += c.nslot) contact_export_item_lds(c, s);
+    }
     NT_TICK(3);
     // -- interval 4: integrate_bodies (unless it ran beside the pairs)
     if (!overlap) {
@@ -236,12 +248,14 @@ __global__ void __launch_bounds__(THREADS, MINW) xpbd_rollout_kernel(KArgs a) {
     if constexpr (BIG) c.aos_records = a.ct.cr != nullptr && !xpbd_keeps_prestep_state(a.p);
     const fused::Ctx<EPB> cf(c, 0);
     const int nb = a.m.nb;
-    load_tile(c, &a.s_in, true);
-    if (c.valid)
-        for (int r = c.slot; r < 6 * nb; r += c.nslot) {
-            a.s_in.body_f[(size_t)r * c.ES + c.env] = 0.0f;
-            a.s_out.body_f[(size_t)r * c.ES + c.env] = 0.0f;
-        }
+    load_tile(c, &a.s_in, true);  // (body_f is not staged: the rollout seeds body_f_tmp with the zeros clear_forces leaves)
+    if constexpr (!Ctx<EPB>::SPEC) {  // (NT_SPEC: behind the substep loop)
+        if (c.valid)
+            for (int r = c.slot; r < 6 * nb; r += c.nslot) {
+                a.s_in.body_f[(size_t)r * c.ES + c.env] = 0.0f;
+                a.s_out.body_f[(size_t)r * c.ES + c.env] = 0.0f;
+            }
+    }
     __syncthreads();
     fused::phase_body_derived(cf);
     c.stage_joint_inc();
@@ -257,6 +271,18 @@ __global__ void __launch_bounds__(THREADS, MINW) xpbd_rollout_kernel(KArgs a) {
         } else {
             do_fused_substep<EPB, CVX>(c, cf, s == a.substeps - 1);
         }
+    }
+    // NT_SPEC: the launch's outputs all leave behind the last barrier, so that no phase waits for a global store -- the Contacts of
+    // the last substep, body_f of both states as clear_forces leaves it (nothing in the launch reads body_f from HBM), the final
+    // state.  The generic instances export in the last substep and zero body_f in the prologue: with the stores moved, the tile of
+    // 32 was measured 5 % slower (profiles/substep_chain_ab.txt).
+    if constexpr (Ctx<EPB>::SPEC) {
+        export_lds_contacts(c);
+        if (c.valid)
+            for (int r = c.slot; r < 6 * nb; r += c.nslot) {
+                a.s_in.body_f[(size_t)r * c.ES + c.env] = 0.0f;
+                a.s_out.body_f[(size_t)r * c.ES + c.env] = 0.0f;
+            }
     }
     store_state(c, (a.substeps & 1) ? a.s_out : a.s_in);
     NT_TICK(9);
