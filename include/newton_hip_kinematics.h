@@ -144,6 +144,49 @@ nt_status nt_eval_inverse_dynamics(const nt_model* m, const nt_state* in, const 
 nt_status nt_eval_inverse_dynamics_tile(const nt_model* m, const nt_state* in, const float* joint_qdd, int32_t flags, float* tau,
                                         const uint8_t* art_mask, int32_t envs_per_block, void* stream);
 
+/* Forward dynamics: the joint accelerations that joint forces and external link wrenches produce -- the inverse of the map above:
+ *   nt_eval_forward_dynamics   (newton_amd.eval_forward_dynamics; the reference has no single call for it)
+ *   H(q) joint_qdd = joint_f + sum_l J_l^T w_l - h(q, q')
+ * H, J_l and h are exactly those of nt_eval_mass_matrix, nt_eval_jacobian and nt_eval_inverse_dynamics (joint_qdd NULL): the public
+ * convention -- a FREE / DISTANCE joint carries the COM velocity -- the rigid-body terms only: no armature, no joint limits, no drives,
+ * no friction.  This is not the acceleration nt_featherstone_step integrates (armature, the solver's internal FREE-joint convention);
+ * for fixed-base chains of 1-dof joints without armature the two coincide.
+ * w_l is the external wrench on link l, read from in->body_f ([6][nb][ES]: force rows 0..2, torque rows 3..5) in the convention the
+ * steppers consume (integrate_bodies, the Featherstone step's body_f_ext): the world-frame force acting at the link's COM and the
+ * world-frame torque about the link's COM.  With c_l the world COM, J_l^T w_l = J_l^T (F, T + c_l x F) for the origin-referenced J_l.
+ *
+ * flags: NT_FD_GRAVITY and NT_FD_VELOCITY as NT_ID_GRAVITY / NT_ID_VELOCITY select the parts of h; NT_FD_BODY_F adds J^T body_f, clear
+ * = in->body_f is not read and may be NULL.  All clear and joint_f NULL: joint_qdd = 0 exactly.
+ * joint_f and joint_qdd: the PUBLIC layout [env_count * na][D] of nt_eval_inverse_dynamics's tau and joint_qdd -- a round trip needs no
+ * reshuffle.  The padding of joint_qdd (an articulation narrower than D) is written as zero by every call; what the padding of joint_f
+ * holds does not matter.  joint_f is read through the pointer at launch time: an in-place update followed by a graph replay takes
+ * effect.  Inputs read: in->body_q, in->joint_q, in->joint_qd (as nt_eval_inverse_dynamics) and, with NT_FD_BODY_F, in->body_f;
+ * nothing is written but joint_qdd and info.
+ * Not positive definite (a Cholesky pivot that is not > 0: a massless leaf link, a non-finite input): that articulation's nda entries
+ * of joint_qdd are written as NaN and its entry of info ([env_count * na] or NULL) is the 1-based local column of the first failing
+ * pivot; every other articulation's entry is 0.  No other articulation is affected in any way, the ones of the same world and
+ * workgroup included: H is factored block by block, a failing pivot is replaced inside its own block only.
+ * One launch of eval_forward_dynamics_kernel on eval_inverse_dynamics_kernel's tile and launch path: that kernel's walk at q'' = 0
+ * gives the link wrenches (the external wrench, carried from the COM to the root link position, is subtracted in the same lane),
+ * its per-dof sum the right-hand side; eval_mass_matrix_kernel's composite inertias and entry items give H in LDS; the Cholesky runs
+ * column by column, column j of every articulation wider than j between two barriers (D barriers), each entry produced by one lane;
+ * L y = rhs and L^T q'' = y by one lane per (environment, articulation).  H never leaves the workgroup.  No atomics, a fixed summation
+ * order, IEEE arithmetic (correctly rounded division and square root, no contraction): every tile computes the same bits, replicated
+ * worlds in equal states give equal bits.
+ * art_mask as for nt_eval_jacobian: the slices of unselected articulations are neither read nor written, in info too.  No scratch
+ * state, no allocation, no synchronisation; recordable by nt_graph_capture_begin / _end.  Errors: those of nt_eval_inverse_dynamics
+ * (null m / in / body_q / joint_q / joint_qd / joint_qdd NT_ERR_INVALID_ARG), NT_ERR_INVALID_ARG for unknown flag bits and for
+ * NT_FD_BODY_F with a null in->body_f, NT_ERR_UNSUPPORTED when not even one environment per workgroup fits the LDS.  The _tile form
+ * names the tile as nt_eval_ik_tile does. */
+#define NT_FD_GRAVITY  1   /* as NT_ID_GRAVITY */
+#define NT_FD_VELOCITY 2   /* as NT_ID_VELOCITY */
+#define NT_FD_BODY_F   4   /* add J^T body_f; clear = body_f is not read and may be NULL */
+nt_status nt_eval_forward_dynamics(const nt_model* m, const nt_state* in, const float* joint_f /* [env_count*na][D] or NULL = 0 */,
+                                   int32_t flags, float* joint_qdd /* out [env_count*na][D] */, int32_t* info /* [env_count*na] or NULL */,
+                                   const uint8_t* art_mask, void* stream);
+nt_status nt_eval_forward_dynamics_tile(const nt_model* m, const nt_state* in, const float* joint_f, int32_t flags, float* joint_qdd,
+                                        int32_t* info, const uint8_t* art_mask, int32_t envs_per_block, void* stream);
+
 /* Batched inverse kinematics (the capability of the reference's newton.ik.IKSolver: position / rotation / joint-limit objectives,
  * Levenberg-Marquardt):
  *   nt_ik_solve           <- newton.ik.IKSolver.step(joint_q_in, joint_q_out, iterations, step_size)     newton/_src/sim/ik/

@@ -483,6 +483,8 @@ SYMBOLS = {
     "nt_eval_mass_matrix_tile": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_state), _P, _P, _P, C.c_int32, _P]),
     "nt_eval_inverse_dynamics": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_state), _P, C.c_int32, _P, _P, _P]),
     "nt_eval_inverse_dynamics_tile": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_state), _P, C.c_int32, _P, _P, C.c_int32, _P]),
+    "nt_eval_forward_dynamics": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_state), _P, C.c_int32, _P, _P, _P, _P]),
+    "nt_eval_forward_dynamics_tile": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_state), _P, C.c_int32, _P, _P, _P, C.c_int32, _P]),
     "nt_ik_solve": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_ik_problem), _P, _P, _P, _P, C.c_int32, C.c_float, _P]),
     "nt_ik_solve_tile": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_ik_problem), _P, _P, _P, _P, C.c_int32, C.c_float, C.c_int32, _P]),
     "nt_frame_sensor": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_state), C.POINTER(nt_state), C.c_float, C.POINTER(nt_frame_sensor_args), _P]),

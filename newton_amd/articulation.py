@@ -753,23 +753,34 @@ def eval_mass_matrix_numpy(model, body_q, joint_q, H=None, body_I_s=None, art_se
         return H
     t = _articulated(model, "eval_mass_matrix")
     E = t.env_count
+    blocks, I_s = _mass_matrix_float64(model, body_q, joint_q)
+    sel = np.ones((E, t.na), dtype=bool) if art_sel is None else np.asarray(art_sel, dtype=bool).reshape(E, t.na)
+    Hv = H.reshape(E, t.na, D, D)
+    for k, (j0, nja, _d0, _nda) in enumerate(_art_ranges(t)):
+        if body_I_s is not None:
+            for i in range(nja):
+                b = int(t.joint_child[j0 + i])
+                body_I_s.reshape(E, t.nb, 6, 6)[sel[:, k], b] = I_s[sel[:, k], b].astype(np.float32)
+        Hv[sel[:, k], k] = blocks[sel[:, k], k].astype(np.float32)
+    return H
+
+
+def _mass_matrix_float64(model, body_q, joint_q):
+    """(H [E, na, D, D], the links' spatial inertias [E, nb, 6, 6]) in float64, before any rounding (homogeneous model)."""
+    t = model.env
+    E, D = t.env_count, _art_dims(model)[1]
     S = _motion_subspace_numpy(model, body_q, joint_q)
     I_s = _spatial_inertia_numpy(model, body_q)
     on = _path_matrix(t)
     dof_joint = np.searchsorted(t.joint_qd_start, np.arange(t.nd), side="right") - 1 if t.nd else np.zeros(0, dtype=np.int64)
-    sel = np.ones((E, t.na), dtype=bool) if art_sel is None else np.asarray(art_sel, dtype=bool).reshape(E, t.na)
-    Hv = H.reshape(E, t.na, D, D)
+    out = np.zeros((E, t.na, D, D))
     for k, (j0, nja, d0, nda) in enumerate(_art_ranges(t)):
         blk = np.zeros((E, D, D))
         for i in range(nja):
             Jl = np.swapaxes(S[:, d0:d0 + nda], 1, 2) * on[j0 + i, dof_joint[d0:d0 + nda]]  # [E, 6, nda]
-            b = int(t.joint_child[j0 + i])
-            blk[:, :nda, :nda] += np.swapaxes(Jl, 1, 2) @ I_s[:, b] @ Jl
-            if body_I_s is not None:
-                body_I_s.reshape(E, t.nb, 6, 6)[sel[:, k], b] = I_s[sel[:, k], b].astype(np.float32)
-        blk = 0.5 * (blk + np.swapaxes(blk, 1, 2))  # (symmetric bit for bit, like the kernel's one value per pair)
-        Hv[sel[:, k], k] = blk[sel[:, k]].astype(np.float32)
-    return H
+            blk[:, :nda, :nda] += np.swapaxes(Jl, 1, 2) @ I_s[:, int(t.joint_child[j0 + i])] @ Jl
+        out[:, k] = 0.5 * (blk + np.swapaxes(blk, 1, 2))  # (symmetric bit for bit, like the kernel's one value per pair)
+    return out, I_s
 
 
 def _device_art_mask(model, art_sel, what):
@@ -1022,7 +1033,20 @@ def eval_inverse_dynamics_numpy(model, body_q, joint_q, joint_qd, joint_qdd=None
     t = _articulated(model, "eval_inverse_dynamics")
     check_ik_supported(model)
     _parent_first(model, "eval_inverse_dynamics")
-    E, nd = t.env_count, t.nd
+    E = t.env_count
+    blocks = _inverse_dynamics_float64(model, body_q, joint_q, joint_qd, joint_qdd, gravity, velocity_terms)
+    sel = np.ones((E, t.na), dtype=bool) if art_sel is None else np.asarray(art_sel, dtype=bool).reshape(E, t.na)
+    tv = tau.reshape(E, t.na, D)
+    for k in range(t.na):
+        tv[sel[:, k], k] = blocks[sel[:, k], k].astype(np.float32)
+    return tau
+
+
+def _inverse_dynamics_float64(model, body_q, joint_q, joint_qd, joint_qdd, gravity, velocity_terms, link_wrench=None):
+    """tau [E, na, D] in float64, before any rounding (homogeneous model).  ``link_wrench`` [E, nb, 6] (optional): an external wrench
+    on each link about the world origin, subtracted from f_l -- tau then holds h - sum_l J_l^T w_l."""
+    t = model.env
+    E, nd, D = t.env_count, t.nd, _art_dims(model)[1]
     S = _motion_subspace_numpy(model, body_q, joint_q)
     I_s = _spatial_inertia_numpy(model, body_q)
     piv = _joint_pivots_numpy(model, body_q, joint_q)
@@ -1035,8 +1059,7 @@ def eval_inverse_dynamics_numpy(model, body_q, joint_q, joint_qd, joint_qdd=None
         for k, (_j0, _nja, d0, nda) in enumerate(ranges):
             qdd[:, d0:d0 + nda] = np.asarray(joint_qdd, dtype=np.float64).reshape(E, t.na, D)[:, k, :nda]
     g = _world_gravity(model) if gravity else np.zeros((E, 3))
-    sel = np.ones((E, t.na), dtype=bool) if art_sel is None else np.asarray(art_sel, dtype=bool).reshape(E, t.na)
-    tv = tau.reshape(E, t.na, D)
+    out = np.zeros((E, t.na, D))
     for k, (j0, nja, d0, nda) in enumerate(ranges):
         blk = np.zeros((E, D))
         for j in range(j0, j0 + nja):
@@ -1070,10 +1093,12 @@ def eval_inverse_dynamics_numpy(model, body_q, joint_q, joint_qd, joint_qdd=None
             f = np.einsum("eij,ej->ei", Il, acc)
             f[:, :3] += np.cross(w, mom[:, :3])
             f[:, 3:] += np.cross(w, mom[:, 3:]) + np.cross(v, mom[:, :3])
+            if link_wrench is not None:
+                f -= link_wrench[:, int(t.joint_child[j])]
             cols = on[j, dof_joint[d0:d0 + nda]]
             blk[:, :nda] += np.einsum("edi,ei->ed", S[:, d0:d0 + nda], f) * cols
-        tv[sel[:, k], k] = blk[sel[:, k]].astype(np.float32)
-    return tau
+        out[:, k] = blk
+    return out
 
 
 def _device_in(model, value, shape, what):
@@ -1183,3 +1208,200 @@ def _eval_id_groups(model, state, joint_qdd, tau, gravity, velocity_terms, art_s
 
     groups.run(go)
     return tau
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# eval_forward_dynamics
+# ---------------------------------------------------------------------------------------------------------------------------------
+NT_FD_GRAVITY, NT_FD_VELOCITY, NT_FD_BODY_F = 1, 2, 4  # include/newton_hip_kinematics.h
+
+
+def _new_or_checked_info(info, count):
+    if info is None:
+        return None
+    if not isinstance(info, np.ndarray) or info.dtype != np.int32 or info.shape != (count,):
+        raise ValueError(f"info must be an int32 numpy array of shape {(count,)}")
+    return info
+
+
+def eval_forward_dynamics_numpy(model, body_q, joint_q, joint_qd, joint_f=None, body_f=None, joint_qdd=None, gravity=True,
+                                velocity_terms=True, info=None, art_sel=None):
+    """Host mirror of eval_forward_dynamics_kernel: joint_qdd [articulation_count, D] from H joint_qdd = joint_f + sum_l J_l^T w_l - h,
+    in float64 from the parts of eval_mass_matrix_numpy, eval_inverse_dynamics_numpy and eval_jacobian_numpy before their rounding, one
+    Cholesky solve per articulation, float32 out.  ``joint_f`` [articulation_count, D] or None (zero); ``body_f`` [body_count, 6]
+    (world-frame force and torque about each link's COM) or None (no external wrench).  A pivot that is not > 0: the articulation's
+    entries are NaN and its ``info`` (int32 [articulation_count], optional) the 1-based column, otherwise 0.  The slices of
+    articulations ``art_sel`` leaves out stay untouched, in ``info`` too."""
+    D = _art_dims(model)[1]
+    A = int(model.articulation_count)
+    joint_qdd = _new_or_checked(joint_qdd, (A, D), "joint_qdd")
+    info = _new_or_checked_info(info, A)
+    if joint_f is not None:
+        joint_f = np.asarray(joint_f)
+        if joint_f.shape != (A, D):
+            raise ValueError(f"joint_f must have shape {(A, D)}")
+    if body_f is not None:
+        body_f = np.asarray(body_f)
+        if body_f.shape != (int(model.body_count), 6):
+            raise ValueError(f"body_f must have shape {(int(model.body_count), 6)}")
+    if getattr(model, "is_heterogeneous", False):
+        parts = model.world_groups.parts
+        bqs, jqs = _split_parts(parts, body_q, "body_count", 7), _split_parts(parts, joint_q, "joint_coord_count")
+        jqds = _split_parts(parts, joint_qd, "joint_dof_count")
+        bfs = [None] * len(parts) if body_f is None else _split_parts(parts, body_f, "body_count", 6)
+        a0 = 0
+        for p, bq, jq, jqd, bf in zip(parts, bqs, jqs, jqds, bfs):
+            a1 = a0 + p.articulation_count
+            if p.articulation_count:
+                sel = None if art_sel is None else np.asarray(art_sel, dtype=bool)[a0:a1]
+                Dp = _art_dims(p)[1]
+                out = np.array(joint_qdd[a0:a1, :Dp])
+                eval_forward_dynamics_numpy(p, bq, jq, jqd, None if joint_f is None else joint_f[a0:a1, :Dp], bf, out, gravity,
+                                            velocity_terms, None if info is None else info[a0:a1], sel)
+                rows = slice(a0, a1) if sel is None else a0 + np.flatnonzero(sel)
+                joint_qdd[rows] = 0.0
+                joint_qdd[rows, :Dp] = out if sel is None else out[sel]
+            a0 = a1
+        return joint_qdd
+    t = _articulated(model, "eval_forward_dynamics")
+    check_ik_supported(model)
+    _parent_first(model, "eval_forward_dynamics")
+    E = t.env_count
+    wrench = None
+    if body_f is not None:  # (F, T) at the COM -> (F, T + c x F) about the world origin: what J_l^T takes
+        bq = np.asarray(body_q, dtype=np.float64).reshape(E, t.nb, 7)
+        cw = bq[..., :3] + _qrot(bq[..., 3:], np.asarray(model.body_com, dtype=np.float64).reshape(E, t.nb, 3))
+        w = np.asarray(body_f, dtype=np.float64).reshape(E, t.nb, 6)
+        wrench = np.concatenate([w[..., :3], w[..., 3:] + np.cross(cw, w[..., :3])], axis=-1)
+    H, _ = _mass_matrix_float64(model, body_q, joint_q)
+    b = -_inverse_dynamics_float64(model, body_q, joint_q, joint_qd, None, gravity, velocity_terms, wrench)
+    if joint_f is not None:
+        b += np.asarray(joint_f, dtype=np.float64).reshape(E, t.na, D)
+    sel = np.ones((E, t.na), dtype=bool) if art_sel is None else np.asarray(art_sel, dtype=bool).reshape(E, t.na)
+    out, inf = joint_qdd.reshape(E, t.na, D), None if info is None else info.reshape(E, t.na)
+    for k, (_j0, _nja, _d0, nda) in enumerate(_art_ranges(t)):
+        for e in np.flatnonzero(sel[:, k]):
+            row, bad = np.zeros(D), 0
+            A_, L = H[e, k, :nda, :nda], np.zeros((nda, nda))
+            for j in range(nda):  # column by column, the kernel's order: the first pivot that is not > 0 is reported
+                p = A_[j, j] - L[j, :j] @ L[j, :j]
+                if not p > 0.0:
+                    bad = j + 1
+                    break
+                L[j, j] = np.sqrt(p)
+                L[j + 1:, j] = (A_[j + 1:, j] - L[j + 1:, :j] @ L[j, :j]) / L[j, j]
+            if bad:
+                row[:nda] = np.nan
+            elif nda:
+                y = np.linalg.solve(L, b[e, k, :nda])  # (triangular systems)
+                row[:nda] = np.linalg.solve(L.T, y)
+            out[e, k] = row.astype(np.float32)
+            if inf is not None:
+                inf[e, k] = bad
+    return joint_qdd
+
+
+def eval_forward_dynamics(model, state, joint_f=None, joint_qdd=None, body_f=False, gravity=True, velocity_terms=True, info=None, mask=None):
+    """Forward dynamics in the convention of :func:`eval_mass_matrix` / :func:`eval_inverse_dynamics`: the joint accelerations
+    ``joint_qdd`` [articulation_count, D] float32 that the joint forces ``joint_f`` [articulation_count, D] (``None``: zero) produce at
+    the state's ``joint_q`` / ``joint_qd``:
+
+        ``H joint_qdd = joint_f + sum_l J_l^T w_l - h(q, qd)``
+
+    with eval_mass_matrix's ``H``, eval_jacobian's ``J`` and eval_inverse_dynamics's bias forces ``h`` -- so
+    ``eval_inverse_dynamics(joint_qdd=eval_forward_dynamics(joint_f))`` returns ``joint_f`` (``body_f`` off).  ``body_f=True`` reads the
+    external link wrenches ``w_l`` from ``state.body_f`` -- what collide and the contact evaluation leave there: world-frame force and
+    torque about each link's COM, the convention the steppers consume.  ``gravity`` / ``velocity_terms`` select the parts of ``h``; all
+    three off and no ``joint_f``: exactly zero.  The rigid-body terms only: no armature, no joint limits, no drives, no friction -- not
+    the acceleration SolverFeatherstone integrates (for fixed-base chains of 1-dof joints without armature the two coincide).
+
+    An articulation whose ``H`` is not positive definite (a massless leaf link, a non-finite input) gets NaN in its entries and the
+    1-based column of the failing pivot in ``info`` (int32 [articulation_count], optional; 0 otherwise); no other articulation is
+    affected.  The padding of ``joint_qdd`` is written as zero on every call; ``mask`` (bool per articulation) leaves the slices of
+    unselected articulations untouched, in ``info`` too.
+
+    Reads ``state.body_q``, ``state.joint_q``, ``state.joint_qd`` (after a maximal-coordinate step call :func:`eval_ik` first) and, with
+    ``body_f=True``, ``state.body_f``.  A ``joint_qdd`` left ``None`` is allocated and returned: a torch tensor on a GPU model, a numpy
+    array (computed in float64) on a host model.  On a GPU model with ``joint_qdd`` (and ``joint_f`` / ``info``, if used) supplied as
+    resident tensors and no ``mask`` the call is one kernel launch on the model's stream (nt_eval_forward_dynamics): no allocation, no
+    synchronisation, it records into ``newton_amd.graph.capture`` -- ``joint_f`` is read at launch time, an in-place update followed by
+    a replay takes effect.  Multi-axis D6 joints as for :func:`eval_ik`."""
+    art_sel = _mask_selection(model, mask, "eval_forward_dynamics")
+    if getattr(model, "is_heterogeneous", False) and getattr(model, "is_gpu", False):
+        return _eval_fd_groups(model, state, joint_f, joint_qdd, body_f, gravity, velocity_terms, info, art_sel)
+    D = _art_dims(model)[1]
+    if not getattr(model, "is_gpu", False):
+        return eval_forward_dynamics_numpy(model, _host_array(state.body_q), _host_array(state.joint_q), _host_array(state.joint_qd),
+                                           None if joint_f is None else _host_array(joint_f),
+                                           _host_array(state.body_f) if body_f else None, joint_qdd, gravity, velocity_terms, info, art_sel)
+    import ctypes as C  # noqa: PLC0415
+
+    import torch  # noqa: PLC0415
+
+    from . import _lib  # noqa: PLC0415
+
+    t = _articulated(model, "eval_forward_dynamics")
+    check_ik_supported(model)
+    _parent_first(model, "eval_forward_dynamics")
+    dm = model.device_model()
+    shape = (t.env_count * t.na, D)
+    fresh = joint_qdd is None
+    joint_qdd = _device_out(model, joint_qdd, shape, "joint_qdd")
+    if joint_f is not None:
+        joint_f = _device_in(model, joint_f, shape, "joint_f")
+    if info is not None and not (hasattr(info, "data_ptr") and info.dtype == torch.int32 and info.is_cuda and info.is_contiguous()
+                                 and tuple(info.shape) == (shape[0],)):
+        raise ValueError(f"info must be a contiguous int32 tensor of shape {(shape[0],)} on the model's device")
+    if fresh and art_sel is not None:
+        joint_qdd.zero_()
+    art_mask = _device_art_mask(model, art_sel, "eval_forward_dynamics")
+    d = state._desc()
+    flags = (NT_FD_GRAVITY if gravity else 0) | (NT_FD_VELOCITY if velocity_terms else 0) | (NT_FD_BODY_F if body_f else 0)
+    _lib.check(dm.lib.nt_eval_forward_dynamics(C.byref(dm.desc), C.byref(d), None if joint_f is None else joint_f.data_ptr(), flags,
+                                               joint_qdd.data_ptr(), None if info is None else info.data_ptr(),
+                                               None if art_mask is None else art_mask.data_ptr(), dm.stream()),
+               "nt_eval_forward_dynamics")
+    return joint_qdd
+
+
+def _eval_fd_groups(model, state, joint_f, joint_qdd, body_f, gravity, velocity_terms, info, art_sel):
+    """Heterogeneous model on the device: one call per world group (_eval_id_groups' pattern); a group's articulations are a slice of
+    the global [articulation_count, D] arrays, padded to the widest group's D."""
+    import torch  # noqa: PLC0415
+
+    groups = model.world_groups
+    parts = groups.parts
+    D = _art_dims(model)[1]
+    A = int(model.articulation_count)
+    dev = parts[0].device_model().device
+    if joint_qdd is None:
+        joint_qdd = torch.zeros((A, D), dtype=torch.float32, device=dev)
+    elif not (hasattr(joint_qdd, "data_ptr") and joint_qdd.dtype == torch.float32 and tuple(joint_qdd.shape) == (A, D)):
+        raise ValueError(f"joint_qdd must be a float32 tensor of shape {(A, D)}")
+    if joint_f is not None:
+        if not hasattr(joint_f, "data_ptr"):
+            joint_f = torch.from_numpy(np.ascontiguousarray(joint_f, dtype=np.float32)).to(dev)
+        if joint_f.dtype != torch.float32 or tuple(joint_f.shape) != (A, D):
+            raise ValueError(f"joint_f must be a float32 tensor of shape {(A, D)}")
+    if info is not None and not (hasattr(info, "data_ptr") and info.dtype == torch.int32 and tuple(info.shape) == (A,)):
+        raise ValueError(f"info must be an int32 tensor of shape {(A,)}")
+    a_edges = np.concatenate([[0], np.cumsum([p.articulation_count for p in parts])])
+
+    def go(i, p):
+        if not p.articulation_count:
+            return
+        a0, a1 = int(a_edges[i]), int(a_edges[i + 1])
+        sel = None if art_sel is None else art_sel[a0:a1]
+        Dp = _art_dims(p)[1]
+        kw = dict(body_f=body_f, gravity=gravity, velocity_terms=velocity_terms, info=None if info is None else info[a0:a1], mask=sel)
+        if Dp == D:  # the group's slice has the global shape: read and written in place
+            eval_forward_dynamics(p, state.parts[i], None if joint_f is None else joint_f[a0:a1], joint_qdd[a0:a1], **kw)
+            return
+        got = eval_forward_dynamics(p, state.parts[i], None if joint_f is None else joint_f[a0:a1, :Dp].contiguous(), None, **kw)
+        rows = torch.arange(a0, a1, device=dev) if sel is None else torch.as_tensor(a0 + np.flatnonzero(sel), device=dev)
+        pick = slice(None) if sel is None else torch.as_tensor(np.flatnonzero(sel), device=dev)
+        joint_qdd[rows] = 0.0
+        joint_qdd[rows, :Dp] = got[pick]
+
+    groups.run(go)
+    return joint_qdd

@@ -1,9 +1,9 @@
 // nt_featherstone.hip -- SolverFeatherstone (step / fused rollout), eval_fk and eval_ik: launch code + C ABI.  The solver's kernels are
 // nt_featherstone_kernels.hpp, their phases nt_featherstone.hpp (namespace ieee); this unit exists so that they are compiled with the
-// default scheduler (see nt_step_preamble.hpp).  eval_ik, eval_jacobian, eval_mass_matrix, eval_inverse_dynamics, ik_solve and frame_sensor (kernels and entry
+// default scheduler (see nt_step_preamble.hpp).  eval_ik, eval_jacobian, eval_mass_matrix, eval_inverse_dynamics, eval_forward_dynamics, ik_solve and frame_sensor (kernels and entry
 // points, include/newton_hip_kinematics.h) live here whole: the headers the stepping unit shares stay as they are.
 // Launch code: the solver's tile choice is fs_launch (a measured rule of its own); every kinematics entry point -- nt_eval_fk and the
-// five _tile entry points -- chooses its tile and launches through ONE function, kin_launch, below the kernels.
+// six _tile entry points -- chooses its tile and launches through ONE function, kin_launch, below the kernels.
 #include "nt_step_preamble.hpp"
 #ifndef NT_EMULATED_GRID
 #include "../../include/newton_hip_kinematics.h"
@@ -768,6 +768,265 @@ __global__ void __launch_bounds__(256) eval_inverse_dynamics_kernel(KArgs a, con
 }
 
 // ------------------------------------------------------------------------------------------------
+// nt_eval_forward_dynamics (contract: include/newton_hip_kinematics.h): H qdd = joint_f + sum_l J_l^T w_l - h.  The two kernels above
+// composed without a trip through HBM: eval_inverse_dynamics_kernel's walk at qdd = 0 gives the link wrenches f_l (the external wrench
+// w_l, carried from the link's COM to the root link position, is subtracted in the same lane), the per-dof sum gives
+// rhs_d = joint_f_d - sum_l S_d . f_l; eval_mass_matrix_kernel's composite inertias and entry items give H; then a Cholesky per
+// articulation, column by column as in ik_solve_kernel, and the two triangular solves.  Tile: id_layout (its joint_qdd rows hold joint_f,
+// then rhs, then y; its tau block receives qdd), then the composite inertias [10][nj] (the link inertias stay: the wrench phase reads
+// them), H (env-major [e][nd][D], factored in place: the strict lower triangle becomes L), the factor's diagonal [nd], the first failing
+// column per articulation [na] and, with NT_FD_BODY_F, the staged body_f [6][nb].
+// H is block diagonal: column j = 0 .. D - 1 of EVERY articulation wider than j is one barrier interval (D intervals, not nd), and a
+// pivot that is not > 0 stays in its own block: it is replaced by 1 so that the interval's arithmetic goes on, the column is recorded,
+// and the articulation's result is NaN.  Every lane of a column forms the pivot of its articulation from the same entries in the same
+// order (the same bits); the lane of the diagonal row stores it.
+// ------------------------------------------------------------------------------------------------
+struct FdLayout {
+    IdLayout I;
+    int Icc, Dg, info, bf;
+};
+__host__ __device__ inline FdLayout fd_layout(const nt_model& m, const bool uni, const bool body_f) {
+    FdLayout X;
+    X.I = id_layout(m, uni);
+    int o = X.I.F.rows;
+    X.Icc = o; o += 10 * m.nj;
+    X.I.F.HW = (m.nd * m.max_art_dofs) | 1;
+    X.I.F.H = o; o += X.I.F.HW;
+    X.Dg = o; o += m.nd;
+    X.info = o; o += m.na;
+    X.bf = o; o += body_f ? 6 * m.nb : 0;
+    X.I.F.rows = o;
+    return X;
+}
+
+// joint_qdd [env_count * na][D] and info [env_count * na] (or NULL); joint_f the layout of joint_qdd or NULL (zero).  art_mask as for
+// eval_ik_kernel.
+template <int EPB>
+__global__ void __launch_bounds__(256) eval_forward_dynamics_kernel(KArgs a, const float* joint_f, int flags, float* joint_qdd, int* info,
+                                                                    const uint8_t* art_mask) {
+    extern __shared__ __align__(16) float lds[];
+    const nt_model& m = a.m;
+    constexpr int N = Ctx<EPB>::N;
+    const bool with_body_f = (flags & NT_FD_BODY_F) != 0;
+    const FdLayout X = fd_layout(m, Ctx<EPB>::UNI, with_body_f);
+    const IdLayout& I = X.I;
+    Ctx<EPB> c(a, lds, I.F.rows);
+    int* extra = c.own_tables(jm_table_ints(m));
+    __syncthreads();
+    jm_build_tables(c, extra);
+    const JmCtx<EPB> f(c, I.F, extra);
+    const int max_depth = f.max_depth(), D = m.max_art_dofs;
+    jm_load(c, I.F);
+    if (c.valid) {
+        if (flags & NT_FD_VELOCITY) stage_rows(c, I.qd, a.s_in.joint_qd, m.nd);
+        else
+            for (int d = c.slot; d < m.nd; d += c.nslot) lds[(I.qd + d) * N + c.e] = 0.0f;
+        if (with_body_f) stage_rows(c, X.bf, a.s_in.body_f, 6 * m.nb);
+        for (int k = c.slot; k < m.na; k += c.nslot) lds[(X.info + k) * N + c.e] = 0.0f;
+    }
+    // joint_f: the tile's articulations out of the public layout, consecutive lanes on consecutive dofs
+    for (int t = 0; t < N * m.na; ++t) {
+        const int e = t / m.na, k = t - e * m.na, env = blockIdx.x * N + e;
+        if (env >= m.env_count) break;
+        if (art_mask && !art_mask[(size_t)env * m.na + k]) continue;
+        const int j0 = m.art_start[k], nja = m.art_start[k + 1] - j0;
+        const int d0 = nja > 0 ? c.T.joint_qd_start[j0] : 0, nda = nja > 0 ? f.qd_end(j0 + nja - 1) - d0 : 0;
+        const float* in = joint_f ? joint_f + (size_t)((size_t)env * m.na + k) * D : nullptr;
+        for (int i = threadIdx.x; i < nda; i += blockDim.x) lds[(I.qdd + d0 + i) * N + e] = in ? in[i] : 0.0f;
+    }
+    __syncthreads();
+    auto selected = [&](int j) { return !art_mask || art_mask[(size_t)c.env * m.na + f.art[j]]; };
+    auto root_pos = [&](int j) { return c.body_q(c.T.joint_child[m.art_start[f.art[j]]]).p; };
+    auto row3 = [&](int off, int j) { return vec3(lds[(off + j) * N + c.e], lds[(off + m.nj + j) * N + c.e], lds[(off + 2 * m.nj + j) * N + c.e]); };
+    auto S_lin = [&](int d) { return vec3(f.S(c.e, 0, d), f.S(c.e, 1, d), f.S(c.e, 2, d)); };
+    auto S_ang = [&](int d) { return vec3(f.S(c.e, 3, d), f.S(c.e, 4, d), f.S(c.e, 5, d)); };
+    auto Icc = [&](int comp, int j) -> float& { return lds[(X.Icc + comp * m.nj + j) * N + c.e]; };
+    auto rhs = [&](int d) -> float& { return lds[(I.qdd + d) * N + c.e]; };
+    auto Dg = [&](int d) -> float& { return lds[(X.Dg + d) * N + c.e]; };
+    auto first_dof = [&](int k) { return c.T.joint_qd_start[m.art_start[k]]; };
+    // (1) S_d, the link inertias and the pivots, about the root link position: eval_inverse_dynamics_kernel's interval (1)
+    if (c.valid) {
+        for (int d = c.slot; d < m.nd; d += c.nslot)
+            if (selected(f.dof_joint[d])) jm_S_item(f, d, root_pos(f.dof_joint[d]));
+        for (int j = c.slot; j < m.nj; j += c.nslot) {
+            if (!selected(j)) continue;
+            jm_inertia_item(f, j, root_pos(j), nullptr);
+            const vec3 p = id_pivot(f, j) - root_pos(j);
+            lds[(I.piv + j) * N + c.e] = p.x; lds[(I.piv + m.nj + j) * N + c.e] = p.y; lds[(I.piv + 2 * m.nj + j) * N + c.e] = p.z;
+        }
+    }
+    __syncthreads();
+    // (2) per (environment, link): eval_inverse_dynamics_kernel's walk with qdd = 0, f_l minus the external wrench about the root link
+    // position; the link's own inertia seeds its composite row
+    if (c.valid)
+        for (int j = c.slot; j < m.nj; j += c.nslot) {
+            if (!selected(j)) continue;
+            const int d0 = first_dof(f.art[j]), d1 = f.qd_end(j);
+            vec3 v, w, al, aw, w_parent;
+            if (flags & NT_FD_GRAVITY) al = -c.gravity();
+            for (int d = d0; d < d1; ++d) {
+                const int jd = f.dof_joint[d];
+                if (!f.on_path(jd, j)) continue;
+                const int ds = c.T.joint_qd_start[jd], type = c.T.joint_type[jd], k = d - ds;
+                if (k == 0) w_parent = w;
+                const bool angular = type == JT_REVOLUTE || type == JT_BALL || ((type == JT_FREE || type == JT_DISTANCE) && k >= 3) ||
+                                     (type == JT_D6 && k >= c.T.joint_lin_count[jd]);
+                const vec3 sv = S_lin(d), sw = S_ang(d), w_frame = type == JT_D6 ? w : w_parent;
+                const float qd = lds[(I.qd + d) * N + c.e];
+                vec3 dtop, dbottom;
+                if (angular) {
+                    const vec3 r = row3(I.piv, jd), p_dot = v + cross(w, r);
+                    dbottom = cross(w_frame, sw);
+                    dtop = cross(p_dot, sw) + cross(r, dbottom);
+                } else {
+                    dtop = cross(w_frame, sv);
+                }
+                al += dtop * qd;
+                aw += dbottom * qd;
+                v += sv * qd;
+                w += sw * qd;
+            }
+            const float mass = f.Ic(0, j);
+            const vec3 hm(f.Ic(1, j), f.Ic(2, j), f.Ic(3, j));
+            const float xx = f.Ic(4, j), xy = f.Ic(5, j), xz = f.Ic(6, j), yy = f.Ic(7, j), yz = f.Ic(8, j), zz = f.Ic(9, j);
+            auto rot = [&](vec3 u) { return vec3(xx * u.x + xy * u.y + xz * u.z, xy * u.x + yy * u.y + yz * u.z, xz * u.x + yz * u.y + zz * u.z); };
+            const vec3 p_lin = v * mass + cross(w, hm), p_ang = cross(hm, v) + rot(w);  // I v
+            vec3 f_lin = (al * mass + cross(aw, hm)) + cross(w, p_lin);
+            vec3 f_ang = (cross(hm, al) + rot(aw)) + (cross(w, p_ang) + cross(v, p_lin));
+            if (with_body_f) {  // body_f: world-frame force and torque about the link's COM
+                const int b = c.T.joint_child[j];
+                const vec3 F = c.lv3(X.bf, 0, m.nb, b), T = c.lv3(X.bf, 3, m.nb, b);
+                const vec3 r = xform_point(c.body_q(b), c.com(b)) - root_pos(j);
+                f_lin = f_lin - F;
+                f_ang = f_ang - (T + cross(r, F));
+            }
+            lds[(I.f + j) * N + c.e] = f_lin.x; lds[(I.f + m.nj + j) * N + c.e] = f_lin.y; lds[(I.f + 2 * m.nj + j) * N + c.e] = f_lin.z;
+            lds[(I.f + 3 * m.nj + j) * N + c.e] = f_ang.x; lds[(I.f + 4 * m.nj + j) * N + c.e] = f_ang.y; lds[(I.f + 5 * m.nj + j) * N + c.e] = f_ang.z;
+            Icc(0, j) = mass;
+            Icc(1, j) = hm.x; Icc(2, j) = hm.y; Icc(3, j) = hm.z;
+            Icc(4, j) = xx; Icc(5, j) = xy; Icc(6, j) = xz; Icc(7, j) = yy; Icc(8, j) = yz; Icc(9, j) = zz;
+        }
+    __syncthreads();
+    // (3) rhs_d = joint_f_d - sum_l S_d . f_l (eval_inverse_dynamics_kernel's interval (4)) shares the first interval of the composite
+    // inertia level loop -- or, on a tree of depth 0, the interval of the H entries: they meet only in the solve
+    if (c.valid)
+        for (int d = c.slot; d < m.nd; d += c.nslot) {
+            const int jd = f.dof_joint[d];
+            if (!selected(jd)) continue;
+            const vec3 sv = S_lin(d), sw = S_ang(d);
+            float acc = 0.0f;
+            for (int l = jd; l < m.art_start[f.art[jd] + 1]; ++l)
+                if (f.on_path(jd, l)) acc += dot(sv, row3(I.f, l)) + dot(sw, row3(I.f + 3 * m.nj, l));
+            rhs(d) = rhs(d) - acc;
+        }
+    for (int lvl = max_depth - 1; lvl >= 0; --lvl) {  // (eval_mass_matrix_kernel's level loop on the composite rows)
+        if (c.valid)
+            for (int j = c.slot; j < m.nj; j += c.nslot) {
+                if (f.depth[j] != lvl || !selected(j)) continue;
+                float acc[10];
+#pragma unroll
+                for (int k = 0; k < 10; ++k) acc[k] = Icc(k, j);
+                for (int ch = m.art_start[f.art[j]]; ch < m.art_start[f.art[j] + 1]; ++ch) {
+                    if (f.anc[ch] != j) continue;
+#pragma unroll
+                    for (int k = 0; k < 10; ++k) acc[k] += Icc(k, ch);
+                }
+#pragma unroll
+                for (int k = 0; k < 10; ++k) Icc(k, j) = acc[k];
+            }
+        __syncthreads();
+    }
+    // H_ij = S_i . (I^c_deeper S_j): eval_mass_matrix_kernel's entry items, both triangles from one lane
+    if (c.valid)
+        for (int item = c.slot; item < m.nd * D; item += c.nslot) {
+            const int i = item / D, lj = item - i * D, ji = f.dof_joint[i];
+            if (!selected(ji)) continue;
+            const int d0 = first_dof(f.art[ji]), j = d0 + lj;
+            if (j > i) continue;
+            const int jj = f.dof_joint[j];
+            const int deep = f.on_path(jj, ji) ? ji : (f.on_path(ji, jj) ? jj : -1);
+            float h = 0.0f;
+            if (deep >= 0) {
+                const vec3 vi = S_lin(i), wi = S_ang(i), vj = S_lin(j), wj = S_ang(j);
+                const float mass = Icc(0, deep);
+                const vec3 hm(Icc(1, deep), Icc(2, deep), Icc(3, deep));
+                const float xx = Icc(4, deep), xy = Icc(5, deep), xz = Icc(6, deep), yy = Icc(7, deep), yz = Icc(8, deep), zz = Icc(9, deep);
+                const vec3 top = vj * mass + cross(wj, hm);
+                const vec3 bottom = cross(hm, vj) + vec3(xx * wj.x + xy * wj.y + xz * wj.z, xy * wj.x + yy * wj.y + yz * wj.z,
+                                                        xz * wj.x + yz * wj.y + zz * wj.z);
+                h = dot(vi, top) + dot(wi, bottom);
+            }
+            f.H(c.e, i, lj) = h;
+            f.H(c.e, j, i - d0) = h;
+        }
+    __syncthreads();
+    // (4) Cholesky in place, per articulation: in interval j the lane of dof row i = d0 + li (li >= j) of an articulation forms the
+    // pivot of column j, stores it (li == j) or divides its own entry L(li, j) by it; rows above the column rest
+    for (int j = 0; j < D; ++j) {
+        if (c.valid)
+            for (int i = c.slot; i < m.nd; i += c.nslot) {
+                const int ji = f.dof_joint[i], k = f.art[ji], d0 = first_dof(k), li = i - d0;
+                if (li < j || !selected(ji)) continue;
+                const int dj = d0 + j;
+                // row dj of L is read once for both sums (on the diagonal lane t repeats p); the loads of four terms leave together
+                float p = f.H(c.e, dj, j), t = f.H(c.e, i, j);
+#pragma unroll 4
+                for (int q = 0; q < j; ++q) {
+                    const float l = f.H(c.e, dj, q);
+                    p -= l * l;
+                    t -= f.H(c.e, i, q) * l;
+                }
+                const bool bad = !(p > 0.0f);
+                if (bad) p = 1.0f;
+                p = sqrtf(p);
+                if (li == j) {
+                    Dg(dj) = p;
+                    float& first_bad = lds[(X.info + k) * N + c.e];
+                    if (bad && first_bad == 0.0f) first_bad = (float)(j + 1);
+                } else {
+                    f.H(c.e, i, j) = t / p;
+                }
+            }
+        __syncthreads();
+    }
+    // (5) L y = rhs, L^T qdd = y: one lane per (environment, articulation), each sum in ascending order
+    if (c.valid)
+        for (int k = c.slot; k < m.na; k += c.nslot) {
+            const int j0 = m.art_start[k], nja = m.art_start[k + 1] - j0;
+            if (nja <= 0 || !selected(j0)) continue;
+            const int d0 = c.T.joint_qd_start[j0], nda = f.qd_end(j0 + nja - 1) - d0;
+            float* out = lds + I.tau * N + c.e * I.TW + d0;
+            if (lds[(X.info + k) * N + c.e] != 0.0f) {
+                for (int i = 0; i < nda; ++i) out[i] = __builtin_nanf("");
+                continue;
+            }
+            for (int i = 0; i < nda; ++i) {
+                float t = rhs(d0 + i);
+#pragma unroll 4
+                for (int q = 0; q < i; ++q) t -= f.H(c.e, d0 + i, q) * rhs(d0 + q);
+                rhs(d0 + i) = t / Dg(d0 + i);
+            }
+            for (int i = nda - 1; i >= 0; --i) {
+                float t = rhs(d0 + i);
+#pragma unroll 4
+                for (int q = i + 1; q < nda; ++q) t -= f.H(c.e, d0 + q, i) * out[q];
+                out[i] = t / Dg(d0 + i);
+            }
+        }
+    __syncthreads();
+    for (int t = 0; t < N * m.na; ++t) {
+        const int e = t / m.na, k = t - e * m.na, env = blockIdx.x * N + e;
+        if (env >= m.env_count) break;
+        if (art_mask && !art_mask[(size_t)env * m.na + k]) continue;
+        const int j0 = m.art_start[k], nja = m.art_start[k + 1] - j0;
+        const int d0 = nja > 0 ? c.T.joint_qd_start[j0] : 0, nda = nja > 0 ? f.qd_end(j0 + nja - 1) - d0 : 0;
+        float* out = joint_qdd + (size_t)((size_t)env * m.na + k) * D;
+        for (int i = threadIdx.x; i < D; i += blockDim.x) out[i] = i < nda ? lds[I.tau * N + e * I.TW + d0 + i] : 0.0f;
+        if (info && threadIdx.x == 0) info[(size_t)env * m.na + k] = (int)lds[(X.info + k) * N + e];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // nt_ik_solve (newton.ik.IKSolver.step; contract: include/newton_hip_kinematics.h): batched Levenberg-Marquardt IK, one problem per
 // environment, all iterations in one launch.  Tile: eval_jacobian_kernel's (poses, parameters, joint_q, S), then the candidate's
 // joint_q' [nc] and poses [7 nb], the residual blocks of the accepted point and of the candidate (position: residual + world point, 6
@@ -1142,7 +1401,7 @@ __global__ void __launch_bounds__(256) ik_solve_kernel(KArgs a, nt_ik_problem P,
 
 // ------------------------------------------------------------------------------------------------
 // kin_launch: the tile rule and the launch of every kinematics entry point (nt_eval_fk, nt_eval_ik_tile, nt_eval_jacobian_tile,
-// nt_eval_mass_matrix_tile, nt_eval_inverse_dynamics_tile, nt_ik_solve_tile).  envs_per_block 0: on replicated worlds (nt_model.params_uniform, UNI_OK) the
+// nt_eval_mass_matrix_tile, nt_eval_inverse_dynamics_tile, nt_eval_forward_dynamics_tile, nt_ik_solve_tile).  envs_per_block 0: on replicated worlds (nt_model.params_uniform, UNI_OK) the
 // uniform-parameter tile of 16 -- ONE block-shared parameter copy, the parameters are four fifths of what the per-environment tile of
 // eval_ik reads -- if it fits the LDS, otherwise the widest per-environment-parameter tile of 16 / 8 / 4 / 1 that fits.  A named width:
 // that per-environment-parameter tile, if it is one of 1 / 4 / 8 / 16 and fits.  Nothing chosen: NT_ERR_UNSUPPORTED, nothing launched.
@@ -1219,6 +1478,31 @@ static nt_status id_launch(const nt_model* m, const nt_state* in, const float* j
         [&](bool uni) { return id_layout(*m, uni).F.rows; },
         [&](auto T, int epb, size_t lds_bytes) {
             return launch_tile(eval_inverse_dynamics_kernel<T>, a, epb, lds_bytes, stream, joint_qdd, (int)flags, tau, art_mask);
+        });
+#endif
+}
+
+// nt_eval_forward_dynamics_tile: argument checks and what it brings to kin_launch
+static nt_status fd_launch(const nt_model* m, const nt_state* in, const float* joint_f, int32_t flags, float* joint_qdd, int32_t* info,
+                           const uint8_t* art_mask, int32_t envs_per_block, hipStream_t stream) {
+    if (!model_ok(m) || !in || !in->body_q || !in->joint_q || !in->joint_qd || !joint_qdd) return NT_ERR_INVALID_ARG;
+    if (flags & ~(NT_FD_GRAVITY | NT_FD_VELOCITY | NT_FD_BODY_F)) return NT_ERR_INVALID_ARG;
+    if ((flags & NT_FD_BODY_F) && !in->body_f) return NT_ERR_INVALID_ARG;
+    if (m->nj <= 0 || m->na <= 0 || !m->art_start || m->max_art_dofs < 0) return NT_ERR_UNSUPPORTED;
+#ifdef NT_DEV_FAST
+    return NT_ERR_UNSUPPORTED;
+#else
+    if (m->max_art_dofs == 0) return NT_OK;  // (no dofs: joint_qdd has no entries)
+    KArgs a = {};
+    a.m = *m;
+    a.s_in = *in;
+    // slot-lanes: one per dof / joint / body, per entry of a dof's H row block; the gather of joint_f and the streaming phase run
+    // workgroup-wide
+    return kin_launch<true>(
+        m, a, envs_per_block, (size_t)topo_ints(*m) + jm_table_ints(*m), imax(imax(m->nb, m->nj), m->nd * m->max_art_dofs),
+        [&](bool uni) { return fd_layout(*m, uni, (flags & NT_FD_BODY_F) != 0).I.F.rows; },
+        [&](auto T, int epb, size_t lds_bytes) {
+            return launch_tile(eval_forward_dynamics_kernel<T>, a, epb, lds_bytes, stream, joint_f, (int)flags, joint_qdd, (int*)info, art_mask);
         });
 #endif
 }
@@ -1431,6 +1715,17 @@ nt_status nt_eval_inverse_dynamics_tile(const nt_model* m, const nt_state* in, c
 nt_status nt_eval_inverse_dynamics(const nt_model* m, const nt_state* in, const float* joint_qdd, int32_t flags, float* tau,
                                    const uint8_t* art_mask, void* stream) {
     return nt_eval_inverse_dynamics_tile(m, in, joint_qdd, flags, tau, art_mask, 0, stream);
+}
+
+// envs_per_block: the tile, by kin_launch's rule (fd_launch)
+nt_status nt_eval_forward_dynamics_tile(const nt_model* m, const nt_state* in, const float* joint_f, int32_t flags, float* joint_qdd,
+                                        int32_t* info, const uint8_t* art_mask, int32_t envs_per_block, void* stream) {
+    return fd_launch(m, in, joint_f, flags, joint_qdd, info, art_mask, envs_per_block, (hipStream_t)stream);
+}
+
+nt_status nt_eval_forward_dynamics(const nt_model* m, const nt_state* in, const float* joint_f, int32_t flags, float* joint_qdd,
+                                   int32_t* info, const uint8_t* art_mask, void* stream) {
+    return nt_eval_forward_dynamics_tile(m, in, joint_f, flags, joint_qdd, info, art_mask, 0, stream);
 }
 
 // envs_per_block: the tile, by kin_launch's rule

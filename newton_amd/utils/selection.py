@@ -1,6 +1,7 @@
 """ArticulationView -- the subset of newton.selection.ArticulationView (newton/_src/utils/selection.py:500-1800) that an RL
 loop calls between steps: per-world getters / setters for root pose and twist, dof positions / velocities / forces and
-link poses, with an optional world mask, plus masked eval_fk / eval_ik / eval_jacobian / eval_mass_matrix / eval_inverse_dynamics.
+link poses, with an optional world mask, plus masked eval_fk / eval_ik / eval_jacobian / eval_mass_matrix / eval_inverse_dynamics /
+eval_forward_dynamics.
 
 With the env-major SoA layout these are not gather/scatter kernels: ``State._soa[name]`` has shape
 ``[comp, slots_per_env, env_stride]``, so "the dofs of every world" is a strided *view* ``soa[0, a:b, :E].T`` (no copy on
@@ -13,7 +14,7 @@ import fnmatch
 
 import numpy as np
 
-from ..articulation import eval_fk, eval_ik, eval_inverse_dynamics, eval_jacobian, eval_mass_matrix
+from ..articulation import eval_fk, eval_forward_dynamics, eval_ik, eval_inverse_dynamics, eval_jacobian, eval_mass_matrix
 from ..enums import JointType
 
 
@@ -225,3 +226,9 @@ class ArticulationView:
         [articulation_count, D] arrays; ``flags``: ``gravity``, ``velocity_terms``); returns the [world, D] slice of this view's
         articulation."""
         return self._art_slice(eval_inverse_dynamics(self.model, state, joint_qdd, tau, mask=self._art_mask(state, mask), **flags))
+
+    def eval_forward_dynamics(self, state, joint_f=None, joint_qdd=None, mask=None, **options):
+        """newton_amd.eval_forward_dynamics restricted to the selected worlds (``joint_f`` and ``joint_qdd`` are the model-wide
+        [articulation_count, D] arrays; ``options``: ``body_f``, ``gravity``, ``velocity_terms``, ``info``); returns the [world, D] slice
+        of this view's articulation."""
+        return self._art_slice(eval_forward_dynamics(self.model, state, joint_f, joint_qdd, mask=self._art_mask(state, mask), **options))

@@ -1,16 +1,18 @@
 #!/usr/bin/env python
-"""MEASUREMENT TOOL -- nt_eval_jacobian, nt_eval_mass_matrix and nt_eval_inverse_dynamics beside nt_eval_fk and nt_eval_ik on the same
-model, same process.
+"""MEASUREMENT TOOL -- nt_eval_jacobian, nt_eval_mass_matrix, nt_eval_inverse_dynamics and nt_eval_forward_dynamics beside nt_eval_fk and
+nt_eval_ik on the same model, same process.
 
     python tools/eval_jacobian_timing.py [--worlds 4096] [--calls 40] [--repeats 7] [--warmup 20] [--peak-gbs X] [--out FILE]
 
 Quadruped scene, outputs in caller tensors.  One HIP event pair around a batch of `--calls` back-to-back launches of one kernel gives a
 per-call time; the kernels take turns batch by batch, `--repeats` (>= 5) batches each; the median and the spread (min .. max) of the
 batches are reported.  Beside each call stand the bytes it must write (J: worlds * 6 L * D * 4; H: worlds * D * D * 4; tau:
-worlds * D * 4) and read (body_q, joint_q; inverse dynamics: joint_qd and joint_qdd too), the time those bytes take at the streaming
+worlds * D * 4; joint_qdd and info: worlds * (D + 1) * 4) and read (body_q, joint_q; inverse dynamics: joint_qd and joint_qdd too;
+forward dynamics: joint_qd, joint_f and body_f -- all three flags are on), the time those bytes take at the streaming
 peak (`--peak-gbs`: what `bench.py --full` prints for this box; default: a device-to-device copy measured here, read + write counted)
 and the ratio of the measured time to that floor.  Prints ONE JSON line and writes it to --out (default
-profiles/eval_jacobian_timing.json; the run with the inverse-dynamics row is profiles/eval_inverse_dynamics_timing.json)."""
+profiles/eval_jacobian_timing.json; the run with the inverse-dynamics row is profiles/eval_inverse_dynamics_timing.json, the one with
+the forward-dynamics row profiles/eval_forward_dynamics_timing.json)."""
 import argparse
 import ctypes as C
 import json
@@ -60,6 +62,8 @@ def measure(worlds, calls, repeats, warmup, peak_gbs):
     src_q, src_qd = pack_soa(model, jq, 1, t.nc), pack_soa(model, jqd, 1, t.nd)
     state = model.state()
     state.joint_q, state.joint_qd = jq, jqd
+    state.body_f = np.concatenate([rng.uniform(-20.0, 20.0, size=(model.body_count, 3)), rng.uniform(-2.0, 2.0, size=(model.body_count, 3))],
+                                  axis=1).astype(np.float32)
     d = state._desc()
     out_q, out_qd = torch.zeros_like(src_q), torch.zeros_like(src_qd)
     L, D = model.max_joints_per_articulation, model.max_dofs_per_articulation
@@ -67,6 +71,8 @@ def measure(worlds, calls, repeats, warmup, peak_gbs):
     H = torch.zeros((worlds * t.na, D, D), dtype=torch.float32, device="cuda:0")
     tau = torch.zeros((worlds * t.na, D), dtype=torch.float32, device="cuda:0")
     qdd = torch.from_numpy(rng.uniform(-5.0, 5.0, size=(worlds * t.na, D)).astype(np.float32)).to("cuda:0")
+    joint_f = torch.from_numpy(rng.uniform(-10.0, 10.0, size=(worlds * t.na, D)).astype(np.float32)).to("cuda:0")
+    fd_qdd, fd_info = torch.zeros_like(tau), torch.zeros(worlds * t.na, dtype=torch.int32, device="cuda:0")
     m, s, st = C.byref(dm.desc), C.byref(d), dm.stream()
     legs = {
         "eval_fk": lambda: _lib.check(lib.nt_eval_fk(m, src_q.data_ptr(), src_qd.data_ptr(), s, st), "nt_eval_fk"),
@@ -75,11 +81,14 @@ def measure(worlds, calls, repeats, warmup, peak_gbs):
         "eval_mass_matrix": lambda: _lib.check(lib.nt_eval_mass_matrix(m, s, H.data_ptr(), None, None, st), "nt_eval_mass_matrix"),
         "eval_inverse_dynamics": lambda: _lib.check(lib.nt_eval_inverse_dynamics(m, s, qdd.data_ptr(), 3, tau.data_ptr(), None, st),
                                                     "nt_eval_inverse_dynamics"),
+        "eval_forward_dynamics": lambda: _lib.check(lib.nt_eval_forward_dynamics(m, s, joint_f.data_ptr(), 7, fd_qdd.data_ptr(),
+                                                                                 fd_info.data_ptr(), None, st), "nt_eval_forward_dynamics"),
     }
     state_bytes = worlds * 4 * (7 * t.nb + t.nc)
     traffic = {"eval_fk": (worlds * 4 * (t.nc + t.nd), worlds * 52 * t.nb), "eval_ik": (worlds * 52 * t.nb, worlds * 4 * (t.nc + t.nd)),
                "eval_jacobian": (state_bytes, J.numel() * 4), "eval_mass_matrix": (state_bytes, H.numel() * 4),
-               "eval_inverse_dynamics": (state_bytes + worlds * 4 * t.nd + qdd.numel() * 4, tau.numel() * 4)}
+               "eval_inverse_dynamics": (state_bytes + worlds * 4 * t.nd + qdd.numel() * 4, tau.numel() * 4),
+               "eval_forward_dynamics": (state_bytes + worlds * 4 * (t.nd + 6 * t.nb) + joint_f.numel() * 4, (fd_qdd.numel() + fd_info.numel()) * 4)}
     for _ in range(warmup):
         for f in legs.values():
             f()
