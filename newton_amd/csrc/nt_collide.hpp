@@ -265,7 +265,15 @@ NT_DI void pair_eval_item(const Ctx<EPB>& c, const int p) {
     const nt_model& m = c.a.m;
     const nt_contacts& ct = c.a.ct;
     const int cpp = m.cpp;
+    constexpr bool SPEC = Ctx<EPB>::SPEC;
     int sa = c.T.pair_a[p], sb = c.T.pair_b[p];
+    if constexpr (SPEC) {
+        // instead: the host's type-sorted order of the pair (pair_desc_words) -- the exchange below never runs, and the AABB test in
+        // front of it is symmetric in the two shapes
+        const int* d = c.T.pair_desc + 4 * p;
+        sa = d[0];
+        sb = d[1];
+    }
     xform Xa, Xb;
     vec3 loa, hia, lob, hib;
     shape_world(c, sa, Xa, loa, hia);
@@ -275,7 +283,7 @@ NT_DI void pair_eval_item(const Ctx<EPB>& c, const int p) {
     int nvalid = 0;
     if (hit) {
         int ta = c.T.shape_type[sa], tb = c.T.shape_type[sb];
-        if (ta > tb) {  // sort by type (narrow_phase.py:525-528)
+        if (!SPEC && ta > tb) {  // sort by type (narrow_phase.py:525-528)
             int t = sa; sa = sb; sb = t;
             t = ta; ta = tb; tb = t;
             xform X = Xa; Xa = Xb; Xb = X;
@@ -307,7 +315,7 @@ NT_DI void pair_eval_item(const Ctx<EPB>& c, const int p) {
             primitive_pair(ta, tb, Xa, Xb, scale_a, scale_b, gap_sum + margin_a + margin_b, k4);
             float total_sep = ra + rb + margin_a + margin_b;
             vec3 n = normalize(k4.normal);
-            if constexpr (STAGED) c.st_lv3(c.L.st, 0, m.np, p, n);
+            if constexpr (STAGED && !SPEC) c.st_lv3(c.L.st, 0, m.np, p, n);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 float dist = k4.dist(i);
@@ -319,7 +327,15 @@ NT_DI void pair_eval_item(const Ctx<EPB>& c, const int p) {
                     float d = dot(bw - aw, n) - total_sep;
                     ok = d <= gap_sum;
                     if (ok) {  // the nvalid-th admitted candidate
-                        if constexpr (STAGED) {
+                        if constexpr (SPEC) {
+                            // parked in the rows of the slot's OWN record (L.cr, outside the scratch union): the lane that solves the
+                            // contact reads them and overwrites them with the finished record (contact_record_make).  The normal
+                            // already sits where the record keeps it
+                            const int ncs = m.np * cpp, slot = p * cpp + nvalid;
+                            c.st_lv3(c.L.cr, CD_NORMAL, ncs, slot, n);
+                            c.st_lv3(c.L.cr, CD_POINT0, ncs, slot, center);
+                            c.l(c.L.cr, CD_POINT1, ncs, slot) = dist;
+                        } else if constexpr (STAGED) {
                             c.st_lv3(c.L.st, 3 + 4 * nvalid, m.np, p, center);
                             c.l(c.L.st, 6 + 4 * nvalid, m.np, p) = dist;
                         } else {
@@ -445,6 +461,42 @@ NT_DI void contact_record_item_lds(const Ctx<EPB>& c, const int entry) {
     c.st_lv3(c.L.cr, CD_NORMAL, ncs, slot, n);
     c.l(c.L.cr, CD_MARGIN0, ncs, slot) = off_a;
     c.l(c.L.cr, CD_MARGIN1, ncs, slot) = off_b;
+}
+// NT_SPEC: the same conversion on the lane that solves the contact next (fused::contact_item in the step's first contact phase), from
+// the candidate its pair lane parked in the slot's own rows of L.cr (pair_eval_item) and the descriptor words the caller has loaded.
+// The record goes to L.cr for the later iterations and the launch's Contacts, and to the caller in r[CD_*] -- no barrier and no reload
+// between record and solve.  Same arithmetic as contact_record_item_lds.
+template <int EPB>
+NT_DI void contact_record_make(const Ctx<EPB>& c, const int slot, const int sa, const int sb, const int ba, const int bb,
+                               float (&r)[NT_CONTACT_FLOATS]) {
+    const nt_model& m = c.a.m;
+    const int ncs = m.np * m.cpp;
+    const int ta = c.T.shape_type[sa], tb = c.T.shape_type[sb];
+    const float ra = (ta == GEO_SPHERE || ta == GEO_CAPSULE) ? c.shape_f(sa, SP_SCALE) : 0.0f;
+    const float rb = (tb == GEO_SPHERE || tb == GEO_CAPSULE) ? c.shape_f(sb, SP_SCALE) : 0.0f;
+    const vec3 n = c.lv3(c.L.cr, CD_NORMAL, ncs, slot);
+    const vec3 center = c.lv3(c.L.cr, CD_POINT0, ncs, slot);
+    const float dist = c.l(c.L.cr, CD_POINT1, ncs, slot);
+    const xform Xbw_a = ba < 0 ? xform() : xform_inverse(c.body_q_in(ba));
+    const xform Xbw_b = bb < 0 ? xform() : xform_inverse(c.body_q_in(bb));
+    const float off_a = ra + c.shape_f(sa, SP_MARGIN), off_b = rb + c.shape_f(sb, SP_MARGIN);
+    const vec3 aw = center - n * (0.5f * dist + ra);
+    const vec3 bw = center + n * (0.5f * dist + rb);
+    const vec3 p0 = xform_point(Xbw_a, aw), p1 = xform_point(Xbw_b, bw);
+    const vec3 o0 = xform_vector(Xbw_a, off_a * n), o1 = xform_vector(Xbw_b, -off_b * n);
+    c.st_lv3(c.L.cr, CD_POINT0, ncs, slot, p0);
+    c.st_lv3(c.L.cr, CD_POINT1, ncs, slot, p1);
+    c.st_lv3(c.L.cr, CD_OFFSET0, ncs, slot, o0);
+    c.st_lv3(c.L.cr, CD_OFFSET1, ncs, slot, o1);
+    c.l(c.L.cr, CD_MARGIN0, ncs, slot) = off_a;
+    c.l(c.L.cr, CD_MARGIN1, ncs, slot) = off_b;
+    r[CD_POINT0] = p0.x; r[CD_POINT0 + 1] = p0.y; r[CD_POINT0 + 2] = p0.z;
+    r[CD_POINT1] = p1.x; r[CD_POINT1 + 1] = p1.y; r[CD_POINT1 + 2] = p1.z;
+    r[CD_OFFSET0] = o0.x; r[CD_OFFSET0 + 1] = o0.y; r[CD_OFFSET0 + 2] = o0.z;
+    r[CD_OFFSET1] = o1.x; r[CD_OFFSET1 + 1] = o1.y; r[CD_OFFSET1 + 2] = o1.z;
+    r[CD_NORMAL] = n.x; r[CD_NORMAL + 1] = n.y; r[CD_NORMAL + 2] = n.z;
+    r[CD_MARGIN0] = off_a;
+    r[CD_MARGIN1] = off_b;
 }
 // ... and at the last substep of the launch the Contacts buffers in HBM receive them (one lane per slot: ids + record, or -1 ids)
 template <int EPB>

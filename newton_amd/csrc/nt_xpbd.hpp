@@ -42,7 +42,7 @@ NT_DI quat xnormalize(quat q) {
     if (l > 0.0f) return q * xrcp(l);
     return quat(0.f, 0.f, 0.f, 1.f);
 }
-template <int EPB>
+template <int EPB, bool ZERO_SKIP = false>
 NT_DI void joint_force_item(const Ctx<EPB>& c, const int j);
 template <int EPB>
 NT_DI void seed_body_forces(const Ctx<EPB>& c, bool forces_are_zero) {
@@ -60,13 +60,32 @@ NT_DI void phase_joint_forces(const Ctx<EPB>& c, bool forces_are_zero) {
     seed_body_forces(c, forces_are_zero);
     for (int j = c.slot; j < c.a.m.nj; j += c.nslot) joint_force_item(c, j);
 }
-template <int EPB>
+// ZERO_SKIP (the NT_SPEC rollout, whose body_f_tmp is seeded with +0): a joint whose joint_f entries are all zero -- every joint of a
+// launch driven through joint targets -- stores the zero wrench without forming the joint frames.  The test is this lane's, on the
+// values it would read; a joint with any non-zero (or NaN) entry takes the full path.  Bit-exact for finite poses: the full path
+// yields wrenches of +-0 there, the integrate lane adds or subtracts them in order onto a +0 seed, and x +- (+-0) = x, (+0) +- (+-0) = +0,
+// an exact cancellation gives +0 -- no sum depends on the sign of a zero wrench.  (A step kernel may be seeded with a user's -0 body_f,
+// so it keeps the full path.  Non-finite poses: the full path makes 0 * inf = NaN of them here, the joint rows of the same step do so
+// from the same poses a few intervals later.)
+template <int EPB, bool ZERO_SKIP>
 NT_DI void joint_force_item(const Ctx<EPB>& c, const int j) {
     const nt_model& m = c.a.m;
     const int nj = m.nj;
     {
         vec3 fp, tp, fc, tc;  // parent wrench (subtracted), child wrench (added)
         int type = c.T.joint_type[j];
+        if constexpr (ZERO_SKIP) {
+            // the rows the full path reads for this joint type, fetched together from clamped indices
+            const int q0 = c.T.joint_qd_start[j];
+            const int n = (type == JT_FREE || type == JT_DISTANCE) ? 6 : type == JT_BALL ? 3 : c.T.joint_lin_count[j] + c.T.joint_ang_count[j];
+            bool any = false;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                const float f = c.l(c.L.cf, 0, 1, q0 + (k < n ? k : 0));
+                any = any || (k < n && f != 0.0f);
+            }
+            if (!any) type = JT_FIXED;  // (no wrench, like a fixed joint's)
+        }
         if (c.T.joint_enabled[j] && type != JT_FIXED && type != JT_ROD) {
             int id_c = c.T.joint_child[j], id_p = c.T.joint_parent[j];
             xform X_pj = c.plxf(c.L.jp, 0, nj, j);
@@ -581,8 +600,24 @@ NT_DI bool contact_solve(const Ctx<EPB>& c, const REC& rec, int shape_a, int sha
 // live_pair >= 0 (fused, staged tiles): the slot is live contact (live_pair, slot - live_pair * cpp) straight from the compacted
 // list, its shapes and bodies come from the pair descriptor -- one LDS round instead of the prefix search and the
 // pair -> shape -> type / body chain.
+// make_record (NT_SPEC, the first contact phase of a step): the slot holds the candidate its pair lane parked, not a record yet -- this
+// lane converts it (ieee::contact_record_make: the collide arithmetic, whichever namespace this copy is compiled in), leaves the record in
+// L.cr for the later iterations and solves from registers.
+template <int EPB>
+NT_DI LoadedRecord make_lds_record(const Ctx<EPB>& c, int slot, int shape_a, int shape_b, int body_a, int body_b) {
+    float r[NT_CONTACT_FLOATS];
+    ieee::contact_record_make(ieee::Ctx<EPB>(c, 0), slot, shape_a, shape_b, body_a, body_b, r);
+    LoadedRecord L;
+    L.p0 = vec3(r[CD_POINT0], r[CD_POINT0 + 1], r[CD_POINT0 + 2]);
+    L.p1 = vec3(r[CD_POINT1], r[CD_POINT1 + 1], r[CD_POINT1 + 2]);
+    L.o0 = vec3(r[CD_OFFSET0], r[CD_OFFSET0 + 1], r[CD_OFFSET0 + 2]);
+    L.o1 = vec3(r[CD_OFFSET1], r[CD_OFFSET1 + 1], r[CD_OFFSET1 + 2]);
+    L.n = vec3(r[CD_NORMAL], r[CD_NORMAL + 1], r[CD_NORMAL + 2]);
+    L.m = r[CD_MARGIN0] + r[CD_MARGIN1];
+    return L;
+}
 template <int EPB, bool FUSED, class CW = CwLds>
-NT_DI void contact_item(const Ctx<EPB>& c, const int slot, const int live_pair = -1) {
+NT_DI void contact_item(const Ctx<EPB>& c, const int slot, const int live_pair = -1, const bool make_record = false) {
     const nt_model& m = c.a.m;
     const nt_contacts& ct = c.a.ct;
     const int cpp = m.cpp, ncs = m.np * cpp;
@@ -593,7 +628,16 @@ NT_DI void contact_item(const Ctx<EPB>& c, const int slot, const int live_pair =
     int shape_a = -1, shape_b = -1, body_a = -1, body_b = -1;
     bool swapped = false, described = false;
     LoadedRecord rec;
-    if (FUSED && live_pair >= 0) {
+    if (Ctx<EPB>::SPEC && FUSED && live_pair >= 0 && make_record) {  // (the descriptor first: the conversion needs it)
+        const int* d = c.T.pair_desc + 4 * live_pair;
+        shape_a = d[0]; shape_b = d[1]; body_a = d[2];
+        const int w = d[3];
+        swapped = (w & (1 << 30)) != 0;
+        body_b = (w << 2) >> 2;
+        live = body_a != body_b;
+        described = true;
+        if constexpr (Ctx<EPB>::SPEC) rec = make_lds_record(c, slot, shape_a, shape_b, body_a, body_b);
+    } else if (FUSED && live_pair >= 0) {
         if (c.lds_records) rec = load_record(LdsRecord<EPB>{c, ncs, slot});
         else rec = load_record(SlotRecord<EPB>{c, ct.data, ncs, slot});  // (a listed contact is live: fetch before anything depends on LDS)
         const int* d = c.T.pair_desc + 4 * live_pair;
@@ -680,17 +724,18 @@ NT_DI CwxSide cwx_side(const Ctx<EPB>& c, int ncs, int slot, int side) {
 // ROWS: the Contacts may carry rows of the SDF legs (nt_contacts.flat) behind the slots -- the launch-by-launch step kernels; the fused
 // rollouts never do and compile without that code
 template <int EPB, bool FUSED, class CW = CwLds, bool ROWS = !FUSED>
-NT_DI void phase_contacts(const Ctx<EPB>& c) {
+NT_DI void phase_contacts(const Ctx<EPB>& c, const bool make_record = false) {
     if (!c.valid) return;
     const int np = c.a.m.np, cpp = c.a.m.cpp;
     if constexpr (FUSED) {
         // lane i takes the environment's i-th live contact (L.px: exclusive prefix of the per-pair live counts); records
         // of dead slots are never written and never read (apply_item stops at the pair's live count)
-        const int total = (int)c.l(c.L.px, 0, 1, np);
+        // (NT_SPEC: the count the pair lanes left in L.lc -- no prefix runs on that tile; make_record: see contact_item)
+        const int total = Ctx<EPB>::SPEC ? *reinterpret_cast<const int*>(&c.l(c.L.lc, 0, 1, 0)) : (int)c.l(c.L.px, 0, 1, np);
         if (c.L.has_lt) {  // the compacted list written with the prefix: no search
             for (int i = c.tslot; i < total; i += c.nslot) {
                 const int e = *reinterpret_cast<const int*>(&c.l(c.L.lt, 0, 1, i));
-                contact_item<EPB, FUSED, CW>(c, (e >> 4) * cpp + (e & 15), e >> 4);
+                contact_item<EPB, FUSED, CW>(c, (e >> 4) * cpp + (e & 15), e >> 4, make_record);
             }
         } else {
             for (int i = c.tslot; i < total; i += c.nslot) {
@@ -1558,7 +1603,8 @@ NT_DI void do_xpbd_step(const Ctx<EPB>& c, bool forces_are_zero) {
     for (int it = 0; it < iterations; ++it) {
         const bool last_it = it == iterations - 1;
         if (has_contacts) {
-            if (!NT_SKIP(4)) phase_contacts<EPB, FUSED, CW, ROWS>(c);
+            // (NT_SPEC: the step's first contact phase also makes the records -- do_fused_substep has no record interval there)
+            if (!NT_SKIP(4)) phase_contacts<EPB, FUSED, CW, ROWS>(c, SPEC && PROLOGUE_DONE && it == 0);
             __syncthreads();
             NT_TICK(5);
             if (rep_contacts) {

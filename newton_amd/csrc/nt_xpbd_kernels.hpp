@@ -86,7 +86,7 @@ NT_DI void do_fused_substep(const Ctx<EPB>& c, const fused::Ctx<EPB>& cf, bool l
             if (i < m.ns) {
                 if (!NT_SKIP(1)) shape_item(c, i);
             } else if (i >= S0) {
-                if (!NT_SKIP(2)) fused::joint_force_item(cf, i - S0);
+                if (!NT_SKIP(2)) fused::joint_force_item<EPB, SPEC>(cf, i - S0);  // (NT_SPEC: all-zero joint_f rows store the zero wrench)
             }
         }
     }
@@ -107,36 +107,42 @@ NT_DI void do_fused_substep(const Ctx<EPB>& c, const fused::Ctx<EPB>& cf, bool l
     __syncthreads();
     NT_TICK(2);
     // -- interval 3: contact records of the analytic pairs (one lane per slot) || live-contact prefix (few lanes per env)
-    if (!NT_SKIP(1) && c.valid && c.lds_records) {
-        // LDS-record tiles: one lane per LIVE contact (the pair lanes built the list), records into L.cr
-        const int total = *reinterpret_cast<const int*>(&c.l(c.L.lc, 0, 1, 0));
-        for (int i = c.slot; i < total; i += c.nslot) contact_record_item_lds(c, *reinterpret_cast<const int*>(&c.l(c.L.lt, 0, 1, i)));
-        if (c.slot == c.nslot - 1) {
-            c.l(c.L.px, 0, 1, m.np) = (float)total;
-            if constexpr (!SPEC) {  // (NT_SPEC: export_lds_contacts, behind the substep loop)
+    // NT_SPEC has no such interval.  Lane i of a world takes live contact i in the record stage AND in the contact phase, so the barrier
+    // between the two ordered a lane against itself; there the step's first contact phase (do_xpbd_step below, behind the barrier
+    // above) makes the record of each contact it takes and solves it from registers.  Ownership rule of that interval: a contact lane
+    // reads and writes the rows of its OWN slots only -- the candidate its pair lane parked in L.cr[slot] one barrier earlier, the
+    // finished record it puts in its place, the correction in L.cw[slot] -- plus state no lane writes in the interval (list and count,
+    // pair_desc, poses, snapshot, body-derived rows).  L.cw overlays the scratch union from its base, which is why the candidates
+    // are parked in L.cr and not in L.st: no lane reads the union here, so no lane's L.cw store can reach a row another wave still
+    // needs.  The list order (L.lt) varies with the waves' timing and decides nothing: every slot has one owner and one record.
+    if constexpr (!SPEC) {
+        if (!NT_SKIP(1) && c.valid && c.lds_records) {
+            // LDS-record tiles: one lane per LIVE contact (the pair lanes built the list), records into L.cr
+            const int total = *reinterpret_cast<const int*>(&c.l(c.L.lc, 0, 1, 0));
+            for (int i = c.slot; i < total; i += c.nslot) contact_record_item_lds(c, *reinterpret_cast<const int*>(&c.l(c.L.lt, 0, 1, i)));
+            if (c.slot == c.nslot - 1) {
+                c.l(c.L.px, 0, 1, m.np) = (float)total;
                 if (last_substep) c.a.ct.env_count[c.env] = total;  // per-env totals: an API-boundary output
             }
-        }
-    } else if (!NT_SKIP(1) && c.valid) {
-        const int nas = m.np_analytic * m.cpp;
-        const int P0 = ((nas + spw - 1) / spw) * spw;
-        const bool one_level = m.np <= 64;
-        if (one_level) {
-            for (int i = c.slot; i < P0 + NT_PREFIX_LANES; i += c.nslot) {
-                if (i < nas) contact_write_item(c, i);
-                else if (i >= P0) prefix_lane(c, i - P0, c.L.sx.off, last_substep, true);
+        } else if (!NT_SKIP(1) && c.valid) {
+            const int nas = m.np_analytic * m.cpp;
+            const int P0 = ((nas + spw - 1) / spw) * spw;
+            const bool one_level = m.np <= 64;
+            if (one_level) {
+                for (int i = c.slot; i < P0 + NT_PREFIX_LANES; i += c.nslot) {
+                    if (i < nas) contact_write_item(c, i);
+                    else if (i >= P0) prefix_lane(c, i - P0, c.L.sx.off, last_substep, true);
+                }
+            } else {
+                for (int s = c.slot; s < nas; s += c.nslot) contact_write_item(c, s);
+                phase_pair_prefix_partials(c, c.L.sx.off);
             }
-        } else {
-            for (int s = c.slot; s < nas; s += c.nslot) contact_write_item(c, s);
-            phase_pair_prefix_partials(c, c.L.sx.off);
         }
-    }
-    __syncthreads();  // also publishes the contact records (global memory) to the block's contact lanes
-    if (!NT_SKIP(1) && m.np > 64 && !c.lds_records) {
-        phase_pair_prefix_scan(c, c.L.sx.off, last_substep, false);
-        __syncthreads();
-    }
-    if constexpr (!SPEC) {  // (NT_SPEC: export_lds_contacts, behind the substep loop)
+        __syncthreads();  // also publishes the contact records (global memory) to the block's contact lanes
+        if (!NT_SKIP(1) && m.np > 64 && !c.lds_records) {
+            phase_pair_prefix_scan(c, c.L.sx.off, last_substep, false);
+            __syncthreads();
+        }
         if (c.lds_records && last_substep && c.valid)  // the launch's Contacts output (reads L.cr / L.pm only: no barrier needed behind it)
             for (int s = c.slot; s < m.np * m.cpp; s += c.nslot) contact_export_item_lds(c, s);
     }
