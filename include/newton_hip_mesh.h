@@ -206,6 +206,70 @@ typedef struct {
 } nt_raycast_args;
 nt_status nt_raycast(const nt_model* m, const nt_state* s, const nt_raycast_args* args, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * nt_camera_render: C cameras of width x height pixels in every world, one launch (newton_amd.sensors.SensorTiledCamera; the
+ * capability of the reference's newton.sensors.SensorTiledCamera without its colour image -- the model carries no shape colours).
+ *
+ * A pixel is a ray of nt_raycast, and everything that comment says about rays, targets, the per-type surfaces, the facing and tie
+ * rules and the error codes holds here word for word; only how the rays are stored differs.  Camera c has ONE origin ray_origins[c]
+ * and ONE frame ray_bodies[c] (env-local body or -1, the same in every world) and a table ray_directions[c][H * W][3] in that frame,
+ * row-major with row 0 at the top of the image; the directions need not be unit.  distance / normal / shape of pixel (c, i, j) of a
+ * world are, BIT FOR BIT, what nt_raycast gives for origin ray_origins[c], direction ray_directions[c][i * W + j] and ray_body
+ * ray_bodies[c] against the same targets and max_distance: the same per-ray instructions in the same order, one lane per pixel.
+ * depth (or NULL) = t * (D . F), D the unit world direction of the pixel and F = forward[c] turned by the body's rotation (forward:
+ * the unit optical axis in the frame of ray_bodies[c]); -1 on a miss.  Outputs are [env_count][C][H][W] (normal: ...[3]).
+ *
+ * Launch shape.  The unit of work is a block of 8 x 8 pixels on one wave (lane l at column l % 8, row l / 8 of the block); the blocks
+ * of a world are numbered over camera, block row, block column: B = C * ceil(H / 8) * ceil(W / 8).  A workgroup has four wave slots
+ * and serves 4 / 2 / 1 worlds for B = 1 / 2 / more (halved while the staged targets do not fit the LDS), i.e. 1 / 2 / 4 slots per
+ * world.  blocks_per_group > 0: every slot takes that many blocks per workgroup item (an item stages its worlds' targets once);
+ * 0: the entry point chooses.  No output bit depends on it.
+ *
+ * Culling (flags bit 0).  block_cones [C][ceil(H / 8) * ceil(W / 8)][5] = (unit axis in the frame of ray_bodies[c], cos h, sin h): a
+ * cone about every ray of the block, h rounded outward; cos h <= 0 switches the block's cull off.  Before a wave walks the targets
+ * it drops the bounded primitives whose bounding sphere (about the staged origin) no ray inside the cone can reach, with a margin far
+ * above the rounding of that test; infinite planes, meshes and heightfields always stay.  The survivors are visited in ascending
+ * slot, so culling changes no output bit; its one observable effect is survivors ([env_count][B] int32 or NULL): the number of
+ * targets the block's wave walked (target_count with the cull off).
+ *
+ * Errors as nt_raycast, plus NT_ERR_INVALID_ARG for camera_count / width / height <= 0, a null table, flags bit 0 without
+ * block_cones, blocks_per_group < 0.  The LDS holds 48 bytes per (world, target) and, above 64 targets, 32 * ceil(K / 64) bytes of
+ * survivor masks.
+ * --------------------------------------------------------------------------------------------------------------------------- */
+#define NT_CAMERA_CULL 1
+#define NT_CAMERA_TILE 8
+typedef struct {
+    int32_t camera_count, width, height; /* C, W, H */
+    const float* ray_origins;          /* [C][3] in the frame of ray_bodies[c] */
+    const int32_t* ray_bodies;         /* [C] env-local body index or -1 (world frame) */
+    const float* ray_directions;       /* [C][H * W][3] in the same frame */
+    const float* forward;              /* [C][3] unit optical axis in the same frame */
+    float max_distance;
+    int32_t target_count;              /* K selected shape slots */
+    const int32_t* targets;            /* DEVICE [K][2] (slot, GeoType), ascending slot */
+    const int32_t* targets_host;       /* HOST   [K][2] the same table (checked before the launch) */
+    const uint8_t* world_mask;         /* [env_count] or NULL */
+    float* distance;                   /* [env_count][C][H][W] */
+    float* depth;                      /* the same shape, or NULL */
+    float* normal;                     /* [env_count][C][H][W][3] or NULL */
+    int32_t* shape;                    /* [env_count][C][H][W] or NULL */
+    /* mesh / heightfield tables, as in nt_raycast_args */
+    const int32_t* shape_vertex_range;
+    const int32_t* shape_triangle_range;
+    const float* vertices;
+    const int32_t* indices;
+    const float* block_bounds;
+    const int32_t* shape_block_start;
+    const int32_t* shape_heightfield_index;
+    const nt_heightfield* heightfields;
+    const float* elevations;
+    const float* block_cones;          /* DEVICE [C][blocks per camera][5], or NULL without NT_CAMERA_CULL */
+    int32_t* survivors;                /* [env_count][B] or NULL */
+    int32_t flags;                     /* NT_CAMERA_CULL */
+    int32_t blocks_per_group;          /* 0: chosen by the entry point */
+} nt_camera_args;
+nt_status nt_camera_render(const nt_model* m, const nt_state* s, const nt_camera_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

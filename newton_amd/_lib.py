@@ -181,6 +181,18 @@ class nt_raycast_args(C.Structure):
                 ("shape_heightfield_index", C.c_void_p), ("heightfields", C.c_void_p), ("elevations", C.c_void_p)]
 
 
+class nt_camera_args(C.Structure):
+    """include/newton_hip_mesh.h: C cameras of width x height pixels per world (newton_amd.sensors.SensorTiledCamera)."""
+    _fields_ = [("camera_count", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("ray_origins", C.c_void_p),
+                ("ray_bodies", C.c_void_p), ("ray_directions", C.c_void_p), ("forward", C.c_void_p), ("max_distance", C.c_float),
+                ("target_count", C.c_int32), ("targets", C.c_void_p), ("targets_host", C.c_void_p), ("world_mask", C.c_void_p),
+                ("distance", C.c_void_p), ("depth", C.c_void_p), ("normal", C.c_void_p), ("shape", C.c_void_p),
+                ("shape_vertex_range", C.c_void_p), ("shape_triangle_range", C.c_void_p), ("vertices", C.c_void_p),
+                ("indices", C.c_void_p), ("block_bounds", C.c_void_p), ("shape_block_start", C.c_void_p),
+                ("shape_heightfield_index", C.c_void_p), ("heightfields", C.c_void_p), ("elevations", C.c_void_p),
+                ("block_cones", C.c_void_p), ("survivors", C.c_void_p), ("flags", C.c_int32), ("blocks_per_group", C.c_int32)]
+
+
 class nt_sdf(C.Structure):
     _fields_ = [("coarse", C.c_void_p), ("subgrid", C.c_void_p), ("slots", C.c_void_p), ("cx", C.c_int32), ("cy", C.c_int32),
                 ("cz", C.c_int32), ("tex_size", C.c_int32), ("subgrid_size", C.c_int32), ("quantization", C.c_int32),
@@ -431,6 +443,7 @@ SYMBOLS = {
     "nt_mesh_plane_pairs": (C.c_int32, [C.POINTER(nt_mesh_plane_args), _P]),
     "nt_mesh_triangle_pairs": (C.c_int32, [C.POINTER(nt_mesh_triangle_args), _P]),
     "nt_raycast": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_state), C.POINTER(nt_raycast_args), _P]),
+    "nt_camera_render": (C.c_int32, [C.POINTER(nt_model), C.POINTER(nt_state), C.POINTER(nt_camera_args), _P]),
     # include/newton_hip_broadphase.h
     "nt_broadphase_nxn_swept": (C.c_int32, [C.POINTER(nt_broadphase_in), C.POINTER(nt_broadphase_motion), _P, _P, C.c_int32, C.c_int32,
                                             C.c_int32, _P, _P, C.c_int32, _P]),

@@ -632,6 +632,194 @@ __global__ void __launch_bounds__(RC_THREADS) raycast_kernel(nt_model m, const f
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// nt_camera_render (newton_amd.sensors.SensorTiledCamera; contract: include/newton_hip_mesh.h): C cameras of W x H pixels per world.
+//
+// MI355X mapping.  A pixel is a ray of raycast_kernel -- the same rc_* functions called in the same order, so the same bits -- but
+// the launch is shaped for images: one WAVE owns a block of 8 x 8 pixels (lane l at column l % 8, row l / 8), whose rays run through
+// the same mesh blocks and heightfield cells together.  The 4 wave slots of a workgroup serve `wpb` = 4 / 2 / 1 worlds (B = 1 / 2 / more
+// blocks per world) with spw = 4 / wpb slots each; a workgroup item is (group of wpb worlds, group of bpg * spw consecutive blocks):
+// it stages the targets of its worlds once (raycast_kernel's 12-word records), then slot s of a world takes the blocks s, s + spw, ...
+// of the group.  Origin, body and optical axis are one per camera: read and transformed once per block, not per ray.  With
+// NT_CAMERA_CULL the wave first tests target lane, lane + 64, ... against the block's cone and ballots a wave-uniform survivor mask
+// (one register pair for K <= 64, else 64-bit words per slot in LDS behind the records); both passes visit the set bits in ascending
+// order, i.e. the survivors in raycast_kernel's order.  One lane produces every value of a pixel; no atomics, no cross-lane arithmetic.
+// ------------------------------------------------------------------------------------------------------------------------------
+constexpr int CAM_SLOTS = RC_THREADS / 64;  // wave slots per workgroup
+constexpr int CAM_CONE = 5;                 // floats per block cone: axis[3], cos h, sin h
+// The items the entry point aims for when it chooses blocks_per_group: 4 workgroups on each of the 256 CUs.
+constexpr long long CAM_TARGET_ITEMS = 1024;
+// Margin of the cone test, in metres: CAM_CULL_REL * (|centre - eye| + r) + CAM_CULL_ABS.  The test adds a handful of fp32 products
+// of magnitude |centre - eye| (a cross product, two dot products, cos h and sin h rounded to fp32, the axis and the rays turned by
+// the same body rotation): its rounding is a few 1e-7 of that distance, and so is the difference between the bounding radius taken
+// here and the surface rc_primitive tests.  1e-3 relative sits three decades above that at every scene scale, and 1e-5 m keeps it
+// there for a target at the eye.  It only ever keeps a target that a sharper test would drop.
+constexpr float CAM_CULL_REL = 1.0e-3f, CAM_CULL_ABS = 1.0e-5f;
+
+// the radius of a sphere about the staged origin that holds the primitive; false: unbounded (an infinite plane), never culled
+NT_DI bool cam_bound(int type, vec3 s, float& r) {
+    const vec3 a = vabs(s);
+    if (type == RC_PLANE) {
+        if (s.x == 0.0f && s.y == 0.0f) return false;
+        r = sqrtf(a.x * a.x + a.y * a.y);
+    } else if (type == RC_SPHERE) r = a.x;
+    else if (type == RC_ELLIPSOID) r = fmaxw(fmaxw(a.x, a.y), a.z);
+    else if (type == RC_BOX) r = length(a);
+    else if (type == RC_CAPSULE) r = a.x + a.y;
+    else if (type == RC_CYLINDER || type == RC_CONE) r = sqrtf(a.x * a.x + a.y * a.y);
+    else return false;
+    return true;
+}
+
+__global__ void __launch_bounds__(RC_THREADS) camera_kernel(nt_model m, const float* body_q, nt_camera_args a, nt_raycast_args tab, int wpb, int bpg) {
+    extern __shared__ __align__(16) float lds[];
+    const int tid = threadIdx.x, lane = tid & 63, slot = tid >> 6, K = a.target_count;
+    const size_t ES = (size_t)m.env_stride, cs = (size_t)m.nb * ES;
+    const int W = a.width, H = a.height, bx = (W + NT_CAMERA_TILE - 1) / NT_CAMERA_TILE, per_cam = bx * ((H + NT_CAMERA_TILE - 1) / NT_CAMERA_TILE);
+    const int B = a.camera_count * per_cam, spw = CAM_SLOTS / wpb, span = bpg * spw;
+    const int block_groups = (B + span - 1) / span, world_groups = (m.env_count + wpb - 1) / wpb, words = (K + 63) / 64;
+    // (K > 64 only) this slot's survivor words, behind the records: wpb * K * 48 bytes, a multiple of 16
+    unsigned long long* mask_lds = reinterpret_cast<unsigned long long*>(lds + (size_t)wpb * K * RC_REC) + (size_t)slot * words;
+    for (long long item = blockIdx.x; item < (long long)world_groups * block_groups; item += gridDim.x) {
+        const int g = (int)(item / block_groups), bg = (int)(item - (long long)g * block_groups);
+        __syncthreads();  // the previous item's records are no longer read
+        // stage: one (world, target) per lane, as raycast_kernel does
+        for (int it = tid; it < wpb * K; it += RC_THREADS) {
+            const int wl = it / K, k = it - wl * K, e = g * wpb + wl;
+            if (e >= m.env_count || (a.world_mask && !a.world_mask[e])) continue;
+            const int tslot = a.targets[2 * k], type = a.targets[2 * k + 1];
+            float* rec = lds + (size_t)it * RC_REC;
+            int* irec = reinterpret_cast<int*>(rec);  // words 10, 11: type, Newton shape id
+            if (tslot < 0 || tslot >= m.ns + m.ng) { irec[10] = 0; irec[11] = -1; continue; }
+            float sp[10];
+            int id;
+            if (tslot < m.ns) {
+                for (int c = 0; c < 10; ++c) sp[c] = m.shape_param[((size_t)c * m.ns + tslot) * ES + e];
+                id = m.shape_local0 + e * m.ns + tslot;
+            } else {
+                for (int c = 0; c < 10; ++c) sp[c] = m.gshape_param[(size_t)(tslot - m.ns) * NT_SHAPE_PARAM_FLOATS + c];
+                id = m.gshape_id[tslot - m.ns];
+            }
+            xform X(vec3(sp[0], sp[1], sp[2]), quat(sp[3], sp[4], sp[5], sp[6]));
+            const int body = m.shape_body[tslot];
+            if (body >= 0 && body < m.nb) {
+                const float* q = body_q + (size_t)body * ES + e;
+                X = xform(vec3(q[0], q[cs], q[2 * cs]), quat(q[3 * cs], q[4 * cs], q[5 * cs], q[6 * cs])) * X;
+            }
+            rec[0] = X.p.x; rec[1] = X.p.y; rec[2] = X.p.z;
+            rec[3] = X.q.x; rec[4] = X.q.y; rec[5] = X.q.z; rec[6] = X.q.w;
+            rec[7] = sp[7]; rec[8] = sp[8]; rec[9] = sp[9];
+            irec[10] = type;
+            irec[11] = id;
+        }
+        __syncthreads();
+        const int wl = slot / spw, e = g * wpb + wl;  // (wave-uniform from here on)
+        if (e >= m.env_count || (a.world_mask && !a.world_mask[e])) continue;
+        const float* recs = lds + (size_t)wl * K * RC_REC;
+        const int b_end = (bg + 1) * span < B ? (bg + 1) * span : B;
+        for (int b = bg * span + (slot - wl * spw); b < b_end; b += spw) {
+            const int cam = b / per_cam, bc = b - cam * per_cam, brow = bc / bx, bcol = bc - brow * bx;
+            const int px = bcol * NT_CAMERA_TILE + (lane & (NT_CAMERA_TILE - 1)), py = brow * NT_CAMERA_TILE + lane / NT_CAMERA_TILE;
+            const bool pixel = px < W && py < H;
+            // the camera: one origin, body and optical axis for every ray of the block
+            const int rb = a.ray_bodies[cam];
+            const bool frame = rb >= -1 && rb < m.nb, attached = frame && rb >= 0;
+            vec3 O = rc_ld3(a.ray_origins + 3 * (size_t)cam);
+            xform X;
+            if (attached) {
+                const float* q = body_q + (size_t)rb * ES + e;
+                X = xform(vec3(q[0], q[cs], q[2 * cs]), quat(q[3 * cs], q[4 * cs], q[5 * cs], q[6 * cs]));
+                O = xform_point(X, O);
+            }
+            // survivors of the block: target lane, lane + 64, ... against the cone turned into the world
+            const float* cone = a.block_cones + CAM_CONE * (size_t)b;
+            const bool cull = (a.flags & NT_CAMERA_CULL) && cone[3] > 0.0f;
+            vec3 A;
+            float cos_h = 0.0f, sin_h = 0.0f;
+            if (cull) {
+                A = rc_ld3(cone);
+                if (attached) A = quat_rotate(X.q, A);
+                cos_h = cone[3];
+                sin_h = cone[4];
+            }
+            unsigned long long mask0 = 0ull;
+            int count = 0;
+            for (int w = 0; w < words; ++w) {
+                const int k = w * 64 + lane;
+                bool keep = false;
+                if (k < K) {
+                    const float* rec = recs + (size_t)k * RC_REC;
+                    const int type = reinterpret_cast<const int*>(rec)[10];
+                    keep = type != 0;
+                    float r;
+                    if (keep && cull && cam_bound(type, vec3(rec[7], rec[8], rec[9]), r)) {
+                        // distance from the centre to the cone's mantle line (never more than to the cone itself) against r + margin
+                        const vec3 v = vec3(rec[0], rec[1], rec[2]) - O;
+                        keep = !(length(cross(v, A)) * cos_h - dot(v, A) * sin_h > r + (CAM_CULL_REL * (length(v) + r) + CAM_CULL_ABS));
+                    }
+                }
+                const unsigned long long mw = __ballot(keep);
+                if (K <= 64) mask0 = mw;
+                else mask_lds[w] = mw;  // (every lane of the wave stores the same word and reads its own store)
+                count += __popcll(mw);
+            }
+            if (a.survivors && lane == 0) a.survivors[(size_t)e * B + b] = count;
+            if (!pixel) continue;  // (no wave-level operation below)
+            vec3 D = rc_ld3(a.ray_directions + 3 * ((size_t)cam * H * W + (size_t)py * W + px));
+            if (attached) D = quat_rotate(X.q, D);
+            const float len = length(D);
+            const bool live = frame && len > 0.0f;
+            RcBest best;
+            best.t = RC_INF; best.id = 0x7fffffff; best.k = -1;
+            if (live) {
+                D = D / len;
+                for (int w = 0; w < words; ++w) {  // primitives, ascending slot
+                    for (unsigned long long mm = K <= 64 ? mask0 : mask_lds[w]; mm; mm &= mm - 1) {
+                        const int k = w * 64 + __ffsll((long long)mm) - 1;
+                        const float* rec = recs + (size_t)k * RC_REC;
+                        const int type = reinterpret_cast<const int*>(rec)[10];
+                        if (type == RC_MESH || type == RC_HFIELD || type == 0) continue;
+                        const quat q(rec[3], rec[4], rec[5], rec[6]);
+                        const vec3 o = quat_rotate_inv(q, O - vec3(rec[0], rec[1], rec[2])), d = quat_rotate_inv(q, D);
+                        float t;
+                        vec3 n;
+                        if (rc_primitive(type, vec3(rec[7], rec[8], rec[9]), o, d, t, n)) rc_offer(best, a.max_distance, t, reinterpret_cast<const int*>(rec)[11], k, n);
+                    }
+                }
+                for (int w = 0; w < words; ++w) {  // meshes and heightfields, ascending slot
+                    for (unsigned long long mm = K <= 64 ? mask0 : mask_lds[w]; mm; mm &= mm - 1) {
+                        const int k = w * 64 + __ffsll((long long)mm) - 1;
+                        const float* rec = recs + (size_t)k * RC_REC;
+                        const int type = reinterpret_cast<const int*>(rec)[10];
+                        if (type != RC_MESH && type != RC_HFIELD) continue;
+                        const quat q(rec[3], rec[4], rec[5], rec[6]);
+                        const vec3 o = quat_rotate_inv(q, O - vec3(rec[0], rec[1], rec[2])), d = quat_rotate_inv(q, D);
+                        if (type == RC_MESH) rc_mesh(tab, reinterpret_cast<const int*>(rec)[11], k, vec3(rec[7], rec[8], rec[9]), o, d, a.max_distance, best);
+                        else rc_hfield(tab, reinterpret_cast<const int*>(rec)[11], k, o, d, a.max_distance, best);
+                    }
+                }
+            }
+            const size_t out = (((size_t)e * a.camera_count + cam) * H + py) * W + px;
+            const bool hit = best.k >= 0;
+            a.distance[out] = hit ? best.t : -1.0f;
+            if (a.depth) {
+                vec3 F = rc_ld3(a.forward + 3 * (size_t)cam);
+                if (attached) F = quat_rotate(X.q, F);
+                a.depth[out] = hit ? best.t * dot(D, F) : -1.0f;
+            }
+            if (a.shape) a.shape[out] = hit ? best.id : -1;
+            if (a.normal) {
+                vec3 n;
+                if (hit) {
+                    const float* rec = recs + (size_t)best.k * RC_REC;
+                    n = quat_rotate(quat(rec[3], rec[4], rec[5], rec[6]), normalize(best.n));
+                }
+                a.normal[3 * out] = n.x; a.normal[3 * out + 1] = n.y; a.normal[3 * out + 2] = n.z;
+            }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" nt_status nt_mesh_plane_pairs(const nt_mesh_plane_args* a, void* stream) {
@@ -691,5 +879,65 @@ extern "C" nt_status nt_raycast(const nt_model* m, const nt_state* s, const nt_r
         return NT_ERR_LAUNCH;
     hipLaunchKernelGGL(raycast_kernel, dim3((unsigned)blocks), dim3(RC_THREADS), lds_bytes, (hipStream_t)stream, *m, (const float*)s->body_q, *a, wpb,
                        RC_THREADS / wpb);
+    return hipGetLastError() == hipSuccess ? NT_OK : NT_ERR_LAUNCH;
+}
+
+extern "C" nt_status nt_camera_render(const nt_model* m, const nt_state* s, const nt_camera_args* a, void* stream) {
+    if (!m || !s || !a || !s->body_q || !a->ray_origins || !a->ray_bodies || !a->ray_directions || !a->forward || !a->distance ||
+        a->camera_count <= 0 || a->width <= 0 || a->height <= 0 || a->target_count < 0 || !(a->max_distance >= 0.0f) || a->blocks_per_group < 0 ||
+        ((a->flags & NT_CAMERA_CULL) && !a->block_cones) || m->env_count <= 0 || m->env_stride < m->env_count || m->nb <= 0 || m->ns < 0 || m->ng < 0)
+        return NT_ERR_INVALID_ARG;
+    const int K = a->target_count;
+    if (K > 0 && (!a->targets || !a->targets_host || !m->shape_body || (m->ns > 0 && !m->shape_param) || (m->ng > 0 && (!m->gshape_param || !m->gshape_id))))
+        return NT_ERR_INVALID_ARG;
+    bool mesh = false, hfield = false, unsupported = false;
+    for (int k = 0, prev = -1; k < K; ++k) {
+        const int slot = a->targets_host[2 * k], type = a->targets_host[2 * k + 1];
+        if (slot <= prev || slot >= m->ns + m->ng) return NT_ERR_INVALID_ARG;
+        prev = slot;
+        mesh = mesh || type == RC_MESH;
+        hfield = hfield || type == RC_HFIELD;
+        unsupported = unsupported || !(type == RC_PLANE || type == RC_HFIELD || type == RC_SPHERE || type == RC_CAPSULE || type == RC_ELLIPSOID ||
+                                       type == RC_CYLINDER || type == RC_BOX || type == RC_MESH || type == RC_CONE);
+    }
+    if (mesh && (!a->shape_vertex_range || !a->shape_triangle_range || !a->vertices || !a->indices)) return NT_ERR_INVALID_ARG;
+    if ((a->block_bounds != nullptr) != (a->shape_block_start != nullptr)) return NT_ERR_INVALID_ARG;
+    if (hfield && (!a->shape_heightfield_index || !a->heightfields || !a->elevations)) return NT_ERR_INVALID_ARG;
+    if (unsupported) return NT_ERR_UNSUPPORTED;
+    const long long B = (long long)a->camera_count * ((a->width + NT_CAMERA_TILE - 1) / NT_CAMERA_TILE) * ((a->height + NT_CAMERA_TILE - 1) / NT_CAMERA_TILE);
+    if (B > 0x7fffffffLL / 64) return NT_ERR_INVALID_ARG;
+    // worlds per workgroup: a world with one / two blocks needs one / two of the four wave slots, while the staged targets fit the CU
+    int wpb = B == 1 ? 4 : (B == 2 ? 2 : 1);
+    const size_t per_world = (size_t)K * RC_REC * sizeof(float), mask_bytes = K > 64 ? (size_t)CAM_SLOTS * ((K + 63) / 64) * 8 : 0;
+    while (wpb > 1 && wpb * per_world + mask_bytes > RC_LDS_BYTES_PER_CU) wpb /= 2;
+    if (per_world + mask_bytes > RC_LDS_BYTES_PER_CU) return NT_ERR_UNSUPPORTED;
+    const size_t lds_bytes = wpb * per_world + mask_bytes > 16 ? wpb * per_world + mask_bytes : 16;
+    // blocks per slot and item: a world's blocks are cut into as many groups as it takes to reach CAM_TARGET_ITEMS items (few worlds
+    // with large images fill the machine), and into ONE group once the worlds alone reach it (many worlds stage their targets once)
+    const int spw = CAM_SLOTS / wpb;
+    const long long world_groups = ((long long)m->env_count + wpb - 1) / wpb, per_slot = (B + spw - 1) / spw;
+    int bpg = a->blocks_per_group;
+    if (bpg == 0) {
+        long long cuts = (CAM_TARGET_ITEMS + world_groups - 1) / world_groups;
+        cuts = cuts < 1 ? 1 : (cuts > per_slot ? per_slot : cuts);
+        bpg = (int)((per_slot + cuts - 1) / cuts);
+    }
+    if (bpg > per_slot) bpg = (int)per_slot;
+#ifdef NT_EMULATED_GRID
+    const long long grid_cap = NT_EMULATED_GRID;
+#else
+    const long long grid_cap = 8192;
+#endif
+    long long blocks = world_groups * ((B + (long long)bpg * spw - 1) / ((long long)bpg * spw));
+    if (blocks > grid_cap) blocks = grid_cap;
+    if (lds_bytes > 48 * 1024 &&
+        hipFuncSetAttribute((const void*)camera_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
+        return NT_ERR_LAUNCH;
+    nt_raycast_args tab = {};  // the mesh / heightfield tables in the shape rc_mesh / rc_hfield read them
+    tab.shape_vertex_range = a->shape_vertex_range; tab.shape_triangle_range = a->shape_triangle_range;
+    tab.vertices = a->vertices; tab.indices = a->indices;
+    tab.block_bounds = a->block_bounds; tab.shape_block_start = a->shape_block_start;
+    tab.shape_heightfield_index = a->shape_heightfield_index; tab.heightfields = a->heightfields; tab.elevations = a->elevations;
+    hipLaunchKernelGGL(camera_kernel, dim3((unsigned)blocks), dim3(RC_THREADS), lds_bytes, (hipStream_t)stream, *m, (const float*)s->body_q, *a, tab, wpb, bpg);
     return hipGetLastError() == hipSuccess ? NT_OK : NT_ERR_LAUNCH;
 }

@@ -3,7 +3,9 @@
 Ray-cast sensors: ``SensorRaycast`` casts R rays per world against the shapes of that world -- a height scan under a robot's base,
 a lidar sweep over the other bodies.  The capability of the reference's ``newton.sensors.SensorRaycast``; that one is a single
 camera, this one is ONE SENSOR PER WORLD of the replicated model, because that is what the batched layout serves: the same R rays
-(or R rays of its own) in every world, attached to a body of that world or fixed in the world frame.
+(or R rays of its own) in every world, attached to a body of that world or fixed in the world frame.  ``SensorTiledCamera`` (after
+it) is the image-shaped launch over the same per-ray code: C cameras of W x H pixels per world, one wave per 8 x 8 pixels
+(nt_camera_render), every pixel bit for bit the ray cast of its ray.
 
 On a GPU model ``SensorRaycast.eval`` is one launch of raycast_kernel (nt_raycast, include/newton_hip_mesh.h -- the contract is written
 there): no allocation, no synchronisation, recordable by ``newton_amd.graph.capture``; the rays are read through resident pointers,
@@ -440,6 +442,289 @@ class SensorRaycast:
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# SensorTiledCamera: C cameras of width x height pixels in every world (nt_camera_render, contract in include/newton_hip_mesh.h)
+# ---------------------------------------------------------------------------------------------------------------------------------
+CAMERA_TILE = 8            # NT_CAMERA_TILE: the pixel block of one wave
+_CONE_INFLATE = 1.0e-6     # rad added to a block cone's half-angle: above the rounding of its axis to float32 (6e-8)
+_CONE_MAX_HALF_ANGLE = np.deg2rad(80.0)  # a wider block is not culled (the test needs cos h comfortably above 0)
+_FORWARD = np.array([0.0, 0.0, -1.0])    # the camera looks along -z; +x is right, +y is up
+
+
+def pinhole_rays(width, height, fov_y):
+    """[height * width, 3] float32 camera-frame directions of a pinhole camera with vertical field of view ``fov_y`` (radians): pixel
+    (row i, column j), row 0 at the top, looks along (((j + 0.5) / W * 2 - 1) tan(fov_y / 2) W / H, (1 - (i + 0.5) / H * 2) tan(fov_y / 2),
+    -1).  Computed in float64 and rounded once; not unit."""
+    W, H = int(width), int(height)
+    if W <= 0 or H <= 0 or not 0.0 < float(fov_y) < np.pi:
+        raise ValueError("pinhole_rays: width and height must be positive and fov_y inside (0, pi)")
+    th = np.tan(0.5 * float(fov_y))
+    x = ((np.arange(W) + 0.5) / W * 2.0 - 1.0) * th * W / H
+    y = (1.0 - (np.arange(H) + 0.5) / H * 2.0) * th
+    d = np.empty((H, W, 3))
+    d[..., 0], d[..., 1], d[..., 2] = x[None, :], y[:, None], -1.0
+    return d.reshape(H * W, 3).astype(np.float32)
+
+
+def camera_block_cones(directions, width, height):
+    """[C, blocks, 5] float32 for ``directions`` [C, H * W, 3] (the float32 table the kernel reads): per 8 x 8 pixel block, numbered
+    over block row then block column, the unit axis of a cone about every unit ray of the block, and cos / sin of its half-angle.
+    float64 inside; the half-angle is rounded outward by _CONE_INFLATE.  (0, 0, 0, -1, 0) -- no cull -- for a block wider than
+    _CONE_MAX_HALF_ANGLE or without a ray of positive length."""
+    W, H, T = int(width), int(height), CAMERA_TILE
+    d = np.asarray(directions, dtype=np.float64).reshape(-1, H, W, 3)
+    by, bx = (H + T - 1) // T, (W + T - 1) // T
+    out = np.zeros((len(d), by * bx, 5), np.float32)
+    out[..., 3] = -1.0
+    for c in range(len(d)):
+        for r in range(by):
+            for q in range(bx):
+                u = d[c, r * T:(r + 1) * T, q * T:(q + 1) * T].reshape(-1, 3)
+                n = np.linalg.norm(u, axis=1)
+                u = u[n > 0.0] / n[n > 0.0, None]
+                if len(u) == 0 or np.linalg.norm(u.sum(axis=0)) == 0.0:
+                    continue
+                axis = (u.sum(axis=0) / np.linalg.norm(u.sum(axis=0))).astype(np.float32).astype(np.float64)  # as the kernel reads it
+                axis_n = axis / np.linalg.norm(axis)
+                half = float(np.max(np.arctan2(np.linalg.norm(np.cross(u, axis_n), axis=1), u @ axis_n))) + _CONE_INFLATE
+                if half < _CONE_MAX_HALF_ANGLE:
+                    out[c, r * bx + q] = [*axis, np.cos(half), np.sin(half)]
+    return out
+
+
+def camera_numpy(model, body_q, ray_origins, ray_bodies, ray_directions, forward, width, height, max_distance, slots, world_mask=None):
+    """The contract of nt_camera_render in float64: ``raycast_numpy`` over the expanded rays (origin and body of camera c repeated for
+    its H * W directions), reshaped to images: (distance [E, C, H, W], depth, normal [E, C, H, W, 3], shape int32).  depth =
+    t (D . F) with D the unit world direction and F the camera's world forward axis; -1 on a miss."""
+    t = model.env
+    E, nb = t.env_count, t.nb
+    W, H = int(width), int(height)
+    rb = np.asarray(ray_bodies, dtype=np.int64).reshape(-1)
+    Cn = len(rb)
+    d = np.asarray(_host_array(ray_directions), dtype=np.float64).reshape(Cn * H * W, 3)
+    o = np.repeat(np.asarray(_host_array(ray_origins), dtype=np.float64).reshape(Cn, 3), H * W, axis=0)
+    dist, normal, shape = raycast_numpy(model, body_q, o, d, np.repeat(rb, H * W), max_distance, slots, world_mask)
+    bq = np.asarray(_host_array(body_q), dtype=np.float64).reshape(E, nb, 7)
+    att = (rb >= 0) & (rb < nb)
+    q = np.where(att[None, :, None], bq[:, np.where(att, rb, 0), 3:], np.array([0.0, 0.0, 0.0, 1.0]))  # [E, C, 4]
+    F = _qrot(q, np.broadcast_to(np.asarray(forward, dtype=np.float64).reshape(1, Cn, 3), (E, Cn, 3)))
+    D = _qrot(q[:, :, None, :], np.broadcast_to(d.reshape(1, Cn, H * W, 3), (E, Cn, H * W, 3)))
+    n = np.linalg.norm(D, axis=-1, keepdims=True)
+    D = D / np.where(n > 0.0, n, 1.0)
+    dist = dist.reshape(E, Cn, H * W)
+    depth = np.where(dist >= 0.0, dist * np.sum(D * F[:, :, None, :], axis=-1), -1.0)
+    return (dist.reshape(E, Cn, H, W), depth.reshape(E, Cn, H, W), normal.reshape(E, Cn, H, W, 3), shape.reshape(E, Cn, H, W))
+
+
+def _check_ray_targets(name, model, slots):
+    """SensorRaycast._check_targets for another sensor: the selected slots must be ray targets."""
+    t = model.env
+    scale = np.asarray(model.shape_scale).reshape(-1, 3)
+    bad = []
+    for slot in slots:
+        gtype = int(t.shape_type[slot])
+        ids = t.shape_local0 + np.arange(t.env_count) * t.ns + slot if slot < t.ns else np.array([int(t.gshape_id[slot - t.ns])])
+        if gtype not in [int(g) for g in RAY_TARGET_TYPES]:
+            bad.append(f"slot {int(slot)} (shape {int(ids[0])}): {GeoType(gtype).name}")
+        elif gtype == GeoType.CYLINDER and np.any(scale[ids, 2] != 0.0):
+            bad.append(f"slot {int(slot)} (shape {int(ids[0])}): barrel CYLINDER")
+    if bad:
+        raise NotImplementedError(f"{name}: these shapes are no ray targets, take them out of shape_mask -- " + "; ".join(bad))
+
+
+def _upload_ray_target_tables(model, types, a, up):
+    """The mesh / heightfield tables the selected target ``types`` need, uploaded with ``up`` and entered into the argument struct
+    ``a`` (the field names of nt_raycast_args), as SensorRaycast builds them: block bounds per distinct mesh."""
+    from . import _lib  # noqa: PLC0415
+
+    if np.any(types == int(GeoType.MESH)):
+        from .mesh import triangle_block_bounds  # noqa: PLC0415
+
+        vr, tr = np.asarray(model.mesh_vertex_range).reshape(-1, 2), np.asarray(model.mesh_triangle_range).reshape(-1, 2)
+        blk_start, blk_of, tables, n_blk = np.zeros(len(vr), np.int32), {}, [], 0
+        for i in range(len(vr)):
+            if tr[i, 1] <= 0:
+                continue
+            key = (int(vr[i, 0]), int(tr[i, 0]), int(tr[i, 1]))
+            if key not in blk_of:
+                blk_of[key] = n_blk
+                tables.append(triangle_block_bounds(np.asarray(model.mesh_vertices)[vr[i, 0]:vr[i, 0] + vr[i, 1]],
+                                                    np.asarray(model.mesh_indices)[tr[i, 0]:tr[i, 0] + tr[i, 1]]))
+                n_blk += len(tables[-1])
+            blk_start[i] = blk_of[key]
+        a.shape_vertex_range, a.shape_triangle_range = up(vr, np.int32).data_ptr(), up(tr, np.int32).data_ptr()
+        a.vertices, a.indices = up(model.mesh_vertices, np.float32).data_ptr(), up(model.mesh_indices, np.int32).data_ptr()
+        a.block_bounds, a.shape_block_start = up(np.concatenate(tables), np.float32).data_ptr(), up(blk_start, np.int32).data_ptr()
+    if np.any(types == int(GeoType.HFIELD)):
+        hf = (_lib.nt_heightfield * model.heightfield_count)()
+        for k, (off, nrow, ncol, hx, hy, zlo, zhi) in enumerate(model.heightfield_data):
+            hf[k] = _lib.nt_heightfield(int(off), int(nrow), int(ncol), float(hx), float(hy), float(zlo), float(zhi))
+        a.shape_heightfield_index = up(model.shape_heightfield_index, np.int32).data_ptr()
+        a.heightfields = up(np.frombuffer(bytes(hf), dtype=np.uint8).copy(), np.uint8).data_ptr()
+        a.elevations = up(model.heightfield_elevations, np.float32).data_ptr()
+
+
+class SensorTiledCamera:
+    """C depth cameras of ``width`` x ``height`` pixels in every world (the capability of the reference's
+    ``newton.sensors.SensorTiledCamera``): the observation of a vision policy, one image per world and camera.
+
+    ``cameras``: a sequence of ``(body, xform)`` exactly as SensorFrameTransform's ``frames`` -- an env-local body (or -1: fixed in the
+    world) and the camera's pose in it, 7 numbers (p, q xyzw) or None.  The same C cameras exist in every world; per-world camera
+    poses are out of scope.  Camera frame: +x right, +y up, looking along -z; pixel (row i, column j) has row 0 at the top.  The lens
+    is a table of camera-frame directions (not necessarily unit): ``rays`` [H * W, 3] or [C, H * W, 3] -- any distortion -- or
+    ``fov_y`` for ``pinhole_rays``; exactly one of the two.  ``shape_mask``, ``exclude_bodies``, ``max_distance``: as SensorRaycast.
+
+    ``eval(state)`` fills, per pixel, ``distance`` [world, C, H, W] (t along the unit ray, -1: miss -- SensorRaycast's values for the
+    same rays, bit for bit on the device), ``depth`` (t times the cosine to the optical axis: the distance along the camera's forward
+    axis, -1: miss), ``normal`` [world, C, H, W, 3] (unit, world frame, zeros on a miss) and ``shape`` (Newton shape id, -1).  There
+    is no colour image: the model carries no shape colours.  ``ray_origins`` [C, 3], ``ray_bodies`` [C] and ``ray_directions``
+    [C, H * W, 3] are exactly what the kernel reads: the body frame, float32, the directions turned by the camera's rotation in float64
+    and rounded once.
+
+    GPU model: resident float32 / int32 tensors, one launch of camera_kernel on the model's stream per ``eval`` (one wave per 8 x 8
+    pixels), no allocation, recordable by ``newton_amd.graph.capture``.  ``cull``: the wave of a block skips the bounded primitives
+    no ray of the block can reach; it changes no output bit.  Host model: float64 / int32 numpy (``camera_numpy``).  Refused with
+    NotImplementedError: heterogeneous models, and a mask that selects a CONVEX_MESH, a GAUSSIAN or a barrel cylinder."""
+
+    def __init__(self, model, cameras, width, height, rays=None, fov_y=None, max_distance=1e3, shape_mask=None, exclude_bodies=(),
+                 want_depth=True, want_normal=True, want_shape=True, cull=True):
+        if getattr(model, "is_heterogeneous", False):
+            raise NotImplementedError("SensorTiledCamera: heterogeneous models are unsupported (one sensor is C cameras in every world of a "
+                                      "replicated model)")
+        t = model.env
+        E, nslot = t.env_count, t.ns + t.ng
+        self.model, self.max_distance = model, float(max_distance)
+        self.width, self.height, self.cull = int(width), int(height), bool(cull)
+        W, H = self.width, self.height
+        if W <= 0 or H <= 0:
+            raise ValueError("SensorTiledCamera: width and height must be positive")
+        if not self.max_distance >= 0.0:
+            raise ValueError("max_distance must be >= 0")
+        cameras = list(cameras)
+        Cn = self.camera_count = len(cameras)
+        if Cn == 0:
+            raise ValueError("SensorTiledCamera: no camera")
+        if (rays is None) == (fov_y is None):
+            raise ValueError("SensorTiledCamera: give exactly one of rays and fov_y")
+        lens = pinhole_rays(W, H, fov_y) if rays is None else np.asarray(_host_array(rays), dtype=np.float32)
+        if lens.shape not in ((H * W, 3), (Cn, H * W, 3)) or not np.all(np.isfinite(lens)):
+            raise ValueError(f"SensorTiledCamera: rays must be finite with shape [{H * W}, 3] or [{Cn}, {H * W}, 3]")
+        self._lens = np.broadcast_to(lens.astype(np.float64), (Cn, H * W, 3))
+        mask = np.ones(nslot, bool) if shape_mask is None else np.asarray(_host_array(shape_mask)).astype(bool).reshape(-1)
+        if mask.shape != (nslot,):
+            raise ValueError(f"shape_mask must have {nslot} entries (env-local shapes, then global shapes)")
+        excluded = [int(b) for b in exclude_bodies]
+        if any(not 0 <= b < t.nb for b in excluded):
+            raise ValueError(f"exclude_bodies: env-local body indices 0 .. {t.nb - 1}")
+        self.shape_mask = mask & ~np.isin(np.asarray(t.shape_body), excluded)
+        self.slots = np.flatnonzero(self.shape_mask).astype(np.int32)
+        _check_ray_targets("SensorTiledCamera", model, self.slots)
+        self.blocks = Cn * ((H + CAMERA_TILE - 1) // CAMERA_TILE) * ((W + CAMERA_TILE - 1) // CAMERA_TILE)
+        self._tables(cameras)
+        self._gpu = bool(getattr(model, "is_gpu", False))
+        if self._gpu:
+            self._init_device(want_depth, want_normal, want_shape)
+        else:
+            self.distance = np.full((E, Cn, H, W), -1.0)
+            self.depth = np.full((E, Cn, H, W), -1.0) if want_depth else None
+            self.normal = np.zeros((E, Cn, H, W, 3)) if want_normal else None
+            self.shape = np.full((E, Cn, H, W), -1, np.int32) if want_shape else None
+
+    def _tables(self, cameras):
+        """The host tables of ``cameras``: what the kernel reads, float32, computed in float64 and rounded once."""
+        if len(cameras) != self.camera_count:
+            raise ValueError(f"SensorTiledCamera: {self.camera_count} cameras expected, got {len(cameras)}")
+        body, xf = _frame_table("SensorTiledCamera", self.model, cameras)
+        q = xf[:, None, 3:] / np.linalg.norm(xf[:, None, 3:], axis=-1, keepdims=True)
+        self.ray_bodies = body
+        self.ray_origins = xf[:, :3].astype(np.float32)
+        self.ray_directions = _qrot(q, self._lens).astype(np.float32)
+        self.forward = _qrot(q[:, 0], np.broadcast_to(_FORWARD, (len(body), 3))).astype(np.float32)
+        self.block_cones = camera_block_cones(self.ray_directions, self.width, self.height)
+
+    # -----------------------------------------------------------------------------------------------------------------------------
+    def _init_device(self, want_depth, want_normal, want_shape):
+        import torch  # noqa: PLC0415
+
+        from . import _lib  # noqa: PLC0415
+
+        model, t = self.model, self.model.env
+        dev = model.device_model().device
+        E, Cn, H, W = t.env_count, self.camera_count, self.height, self.width
+        self._keep = []
+
+        def up(a, dtype):
+            x = torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
+            if x.numel() == 0:
+                x = torch.zeros(1, dtype=x.dtype, device=dev)
+            self._keep.append(x)
+            return x
+
+        self._resident = {k: up(getattr(self, k), np.int32 if k == "ray_bodies" else np.float32)
+                          for k in ("ray_origins", "ray_bodies", "ray_directions", "forward", "block_cones")}
+        self.distance = torch.full((E, Cn, H, W), -1.0, dtype=torch.float32, device=dev)
+        self.depth = torch.full((E, Cn, H, W), -1.0, dtype=torch.float32, device=dev) if want_depth else None
+        self.normal = torch.zeros((E, Cn, H, W, 3), dtype=torch.float32, device=dev) if want_normal else None
+        self.shape = torch.full((E, Cn, H, W), -1, dtype=torch.int32, device=dev) if want_shape else None
+        self._world_mask = torch.ones(E, dtype=torch.uint8, device=dev)
+        types = np.asarray(t.shape_type)[self.slots]
+        self._targets_host = np.ascontiguousarray(np.stack([self.slots, types], axis=1), dtype=np.int32).reshape(-1, 2)
+        a = _lib.nt_camera_args()
+        a.camera_count, a.width, a.height = Cn, W, H
+        for k in ("ray_origins", "ray_bodies", "ray_directions", "forward", "block_cones"):
+            setattr(a, k, self._resident[k].data_ptr())
+        a.max_distance, a.target_count = self.max_distance, len(self.slots)
+        a.targets, a.targets_host = up(self._targets_host, np.int32).data_ptr(), self._targets_host.ctypes.data
+        for k in ("distance", "depth", "normal", "shape"):
+            setattr(a, k, None if getattr(self, k) is None else getattr(self, k).data_ptr())
+        a.flags = 1 if self.cull else 0  # NT_CAMERA_CULL
+        _upload_ray_target_tables(model, types, a, up)
+        self._args = a
+
+    def set_cameras(self, cameras):
+        """New ``(body, xform)`` of the same C cameras: the tables and the cull cones are recomputed and copied into the resident
+        arrays (a captured graph sees the new poses on its next replay)."""
+        self._tables(list(cameras))
+        if self._gpu:
+            import torch  # noqa: PLC0415
+
+            for k, dst in self._resident.items():
+                dst.copy_(torch.from_numpy(np.ascontiguousarray(getattr(self, k))).reshape(dst.shape))
+
+    def eval(self, state, world_mask=None):
+        """Render from ``state.body_q``.  ``world_mask`` ([world] bool): the images of unselected worlds are neither computed nor
+        written.  GPU model: one kernel launch on the model's stream (the mask is copied into a resident buffer first)."""
+        t = self.model.env
+        if world_mask is not None and int(np.prod(np.shape(world_mask))) != t.env_count:
+            raise ValueError(f"world_mask must have {t.env_count} entries")
+        if self._gpu:
+            from . import _lib  # noqa: PLC0415
+            from .state import State  # noqa: PLC0415
+
+            if not isinstance(state, State):
+                raise TypeError("SensorTiledCamera.eval: a GPU model needs a State (body_q is read on the device)")
+            dm = self.model.device_model()
+            if world_mask is not None:
+                import torch  # noqa: PLC0415
+
+                wm = world_mask if hasattr(world_mask, "data_ptr") else torch.from_numpy(np.asarray(world_mask).astype(np.uint8))
+                self._world_mask.copy_(wm.reshape(-1).to(torch.uint8))
+            self._args.world_mask = None if world_mask is None else self._world_mask.data_ptr()
+            d = state._desc()
+            st = dm.lib.nt_camera_render(C.byref(dm.desc), C.byref(d), C.byref(self._args), dm.stream())
+            if st == -3:  # NT_ERR_UNSUPPORTED
+                raise NotImplementedError("SensorTiledCamera.eval: nt_camera_render answered NT_ERR_UNSUPPORTED (the selected shapes of one "
+                                          "world do not fit the LDS, or a shape type is no ray target)")
+            _lib.check(st, "nt_camera_render")
+            return
+        got = camera_numpy(self.model, state.body_q, self.ray_origins, self.ray_bodies, self.ray_directions, self.forward, self.width,
+                           self.height, self.max_distance, self.slots, world_mask)
+        sel = slice(None) if world_mask is None else np.asarray(_host_array(world_mask)).astype(bool).reshape(-1)
+        for dst, src in zip((self.distance, self.depth, self.normal, self.shape), got):
+            if dst is not None:
+                dst[sel] = src[sel]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 # SensorContact: net contact force per world on chosen bodies / shapes, split by counterpart (nt_contact_sensor, contract in
 # include/newton_hip_contacts.h)
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -676,6 +961,23 @@ def frame_sensor_numpy(model, body_q, body_qd, frame_body, frame_xform, out_fram
     return out
 
 
+def _frame_table(name, model, table):
+    """[(body, xform or None)] checked for sensor ``name``: (body [M] int32, xform [M, 7] float64)."""
+    nb = model.env.nb
+    bodies, xforms = np.zeros(len(table), np.int32), np.zeros((len(table), 7))
+    for k, (body, xf) in enumerate(table):
+        body = int(body)
+        if not -1 <= body < nb:
+            raise ValueError(f"{name}: frame {k}: body {body} is out of range (env-local 0 .. {nb - 1}, or -1 for the world)")
+        xf = np.array([0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0]) if xf is None else np.asarray(_host_array(xf), dtype=np.float64).reshape(-1)
+        if xf.shape != (7,) or not np.all(np.isfinite(xf)):
+            raise ValueError(f"{name}: frame {k}: xform must be 7 finite numbers (p, q xyzw) or None")
+        if abs(np.linalg.norm(xf[3:]) - 1.0) > _QUAT_NORM_TOL:
+            raise ValueError(f"{name}: frame {k}: the quaternion of xform is not a unit quaternion (norm {np.linalg.norm(xf[3:]):.6g})")
+        bodies[k], xforms[k] = body, xf
+    return bodies, xforms
+
+
 class _FrameSensor:
     """What SensorFrameTransform and SensorIMU share: the frame table, its checks, the resident outputs and the one launch."""
 
@@ -687,18 +989,8 @@ class _FrameSensor:
         t = model.env
         self.model = model
         M = len(table)
-        self.frame_body = np.zeros(M, np.int32)
-        self.frame_xform = np.zeros((M, 7), np.float32)
-        for k, (body, xf) in enumerate(table):
-            body = int(body)
-            if not -1 <= body < t.nb:
-                raise ValueError(f"{name}: frame {k}: body {body} is out of range (env-local 0 .. {t.nb - 1}, or -1 for the world)")
-            xf = np.array([0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0]) if xf is None else np.asarray(_host_array(xf), dtype=np.float64).reshape(-1)
-            if xf.shape != (7,) or not np.all(np.isfinite(xf)):
-                raise ValueError(f"{name}: frame {k}: xform must be 7 finite numbers (p, q xyzw) or None")
-            if abs(np.linalg.norm(xf[3:]) - 1.0) > _QUAT_NORM_TOL:
-                raise ValueError(f"{name}: frame {k}: the quaternion of xform is not a unit quaternion (norm {np.linalg.norm(xf[3:]):.6g})")
-            self.frame_body[k], self.frame_xform[k] = body, xf
+        self.frame_body, xf = _frame_table(name, model, table)
+        self.frame_xform = xf.astype(np.float32)
         self.out_frame = np.ascontiguousarray(out_frame, dtype=np.int32)
         self.out_ref = np.ascontiguousarray(out_ref, dtype=np.int32)
         E, N = t.env_count, len(self.out_frame)
