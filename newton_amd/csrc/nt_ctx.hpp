@@ -19,6 +19,19 @@ constexpr int NT_SPEC = 512;
 #define NT_ASSUME(x) ((void)0)
 #endif
 #endif
+// NT_SPEC lane roles: what a lane of that instance is for the whole launch, and the launch-invariant operands of that role, held in
+// registers.  A lane's body is fixed there (phase_apply: slot s is angular body s, slot B0 + s linear body s), and what the record
+// copies -- the topology region, the block-shared parameter copy -- is written by the prologue alone (bind_topology / load_tile) and by
+// no phase.  fused::fill_lane_roles fills it once per launch behind the barriers that publish those regions, from a clamped index (lanes
+// without a role read in range and never look at the result), so nothing outlives a launch: parameter edits, new targets and graph
+// replays need no invalidation.  Plain values (bit copies of the loaded words); only the XPBD phases' copy of this file uses them.
+struct BodyRole {  // the body of an angular lane [0, nb) or a linear lane [B0, B0 + nb) of the apply phases
+    int flags;
+    int pair_start, pair_count, pair_code0;  // T.body_pair_start[b], the length of the body's list, its first entry (clamped)
+    int joint_start, joint_count;            // T.body_joint_start[b], the length of the body's list
+    float inv_mass;
+    float inv_inertia[9], inertia[9];
+};
 template <int EPB>
 struct Ctx {
     static constexpr int N = EPB & 255;
@@ -49,6 +62,8 @@ struct Ctx {
     // launch-invariant slot ranges (first slot of the second population of a shared interval, on a wave boundary), computed once here
     // instead of in every barrier interval.  Read by the NT_SPEC instance only; everywhere else the phases derive them in place
     struct Ranges { int B0, S0, I0, A0; } R;  // linear body lanes, joint-force lanes, integrate lanes, angular joint lanes
+    // the lane's role (NT_SPEC only: fused::fill_lane_roles on the XPBD phases' context; never set, copied or read anywhere else)
+    BodyRole rb;
 
     // rows: float rows per env in front of the block-shared topology ints (-1: the XPBD / collide layout)
     // defer_image: the kernel calls load_tile next (see issue_image)
@@ -343,6 +358,15 @@ struct Ctx {
         mat33 R = quat_to_matrix(q);
         mat33 Ii = inv_inertia(b);
         // T = I^-1 R^T ; W = R T
+        vec3 t0 = Ii * vec3(R.m00, R.m01, R.m02), t1 = Ii * vec3(R.m10, R.m11, R.m12), t2 = Ii * vec3(R.m20, R.m21, R.m22);
+        vec3 r0(R.m00, R.m01, R.m02), r1(R.m10, R.m11, R.m12), r2(R.m20, R.m21, R.m22);
+        l(L.bd, 3, nb, b) = dot(r0, t0); l(L.bd, 4, nb, b) = dot(r0, t1); l(L.bd, 5, nb, b) = dot(r0, t2);
+        l(L.bd, 6, nb, b) = dot(r1, t1); l(L.bd, 7, nb, b) = dot(r1, t2); l(L.bd, 8, nb, b) = dot(r2, t2);
+    }
+    // the same with the body-frame inverse inertia in the caller's registers (NT_SPEC lane roles: BodyRole::inv_inertia)
+    NT_DI void update_body_w(int b, quat q, const mat33& Ii) const {
+        const int nb = a.m.nb;
+        mat33 R = quat_to_matrix(q);
         vec3 t0 = Ii * vec3(R.m00, R.m01, R.m02), t1 = Ii * vec3(R.m10, R.m11, R.m12), t2 = Ii * vec3(R.m20, R.m21, R.m22);
         vec3 r0(R.m00, R.m01, R.m02), r1(R.m10, R.m11, R.m12), r2(R.m20, R.m21, R.m22);
         l(L.bd, 3, nb, b) = dot(r0, t0); l(L.bd, 4, nb, b) = dot(r0, t1); l(L.bd, 5, nb, b) = dot(r0, t2);

@@ -42,6 +42,8 @@ NT_DI quat xnormalize(quat q) {
     if (l > 0.0f) return q * xrcp(l);
     return quat(0.f, 0.f, 0.f, 1.f);
 }
+// values of an NT_SPEC lane-role record (nt_ctx.hpp: plain floats) as the math type the phases compute with
+NT_DI mat33 role_mat33(const float (&v)[9]) { return mat33(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8]); }
 template <int EPB, bool ZERO_SKIP = false>
 NT_DI void joint_force_item(const Ctx<EPB>& c, const int j);
 template <int EPB>
@@ -766,15 +768,21 @@ NT_DI void phase_contacts(const Ctx<EPB>& c, const bool make_record = false) {
 // (it holds q1) also rebuilds the body origin p and the entry-form world COM, the linear lane leaves the COM alone.
 constexpr int NT_APPLY_SLOTS = 5;   // contact slots of a pair fetched together (cpp <= 5)
 constexpr int NT_APPLY_JOINTS = 4;  // incident joints fetched together; longer lists finish in a loop
-template <int EPB, bool FROM_CONTACTS, class CW = CwLds, bool FUSED = false, bool ROWS = !FUSED, bool DEAD_W = false>
+// ROLE (NT_SPEC, whose apply lanes make one trip): b is the body of the lane's role record c.rb -- inverse mass, flags, the two inertia
+// tensors on the angular lane and the heads of its pair / joint lists come from registers instead of two or three dependent rounds of
+// LDS reads in front of the first correction record.  Same values, same arithmetic, same summation order.  The centre of mass stays a
+// load: the last apply rotates it twice (origin, then world COM) from two loads the optimiser keeps apart, and one register copy would
+// let it merge the two rotations, whose products could then contract differently (a precaution: fp contract(fast) decides per use).
+template <int EPB, bool FROM_CONTACTS, class CW = CwLds, bool FUSED = false, bool ROWS = !FUSED, bool DEAD_W = false, bool ROLE = false>
 NT_DI void apply_item(const Ctx<EPB>& c, const int b, const bool do_lin, const bool do_ang, const bool last) {
     const nt_model& m = c.a.m;
     const int nb = m.nb;
+    const BodyRole& role = c.rb;
     const bool need_p = last && do_ang;
     const bool want_lin = do_lin || need_p;
-    float inv_m = c.inv_mass(b);
+    float inv_m = ROLE ? role.inv_mass : c.inv_mass(b);
     if (inv_m == 0.0f) {  // pass-through; an immovable body that integrate_bodies still moved (v != 0) gets its origin back
-        if (need_p && !(c.T.body_flags[b] & BODY_KINEMATIC)) {
+        if (need_p && !((ROLE ? role.flags : c.T.body_flags[b]) & BODY_KINEMATIC)) {
             const quat q = c.body_rot(b);
             const xform X(c.world_com(b) - quat_rotate(q, c.com(b)), q);
             c.st_lv3(c.L.bq, 0, nb, b, X.p);
@@ -787,8 +795,9 @@ NT_DI void apply_item(const Ctx<EPB>& c, const int b, const bool do_lin, const b
     float inv_weight = 0.0f;
     if (FROM_CONTACTS) {
         const int cpp = m.cpp, ncs = m.np * cpp;
-        for (int i = c.T.body_pair_start[b]; i < c.T.body_pair_start[b + 1]; ++i) {
-            int code = c.T.body_pair_list[i];
+        // (ROLE: the list's bounds and its first entry from the record; a body with several pairs reads the later entries as before)
+        for (int i = ROLE ? role.pair_start : c.T.body_pair_start[b]; i < (ROLE ? role.pair_start + role.pair_count : c.T.body_pair_start[b + 1]); ++i) {
+            int code = ROLE && i == role.pair_start ? role.pair_code0 : c.T.body_pair_list[i];
             int p = code >> 1, side = code & 1;  // side 0: this body owns pair_a's shape
             const int live = FUSED ? (int)c.l(c.L.pm, 0, m.np, p) : cpp;  // fused: only live slots carry a record
             // the pair's slots together: one LDS round for the flags, one for the records (a load / wait / branch per slot cost the
@@ -844,7 +853,7 @@ NT_DI void apply_item(const Ctx<EPB>& c, const int b, const bool do_lin, const b
         // angular-row term already signed), so they are summed from ONE base address with immediate offsets -- the first
         // NT_APPLY_JOINTS as one batch of loads (clamped entry, predicated add), longer lists in a loop
         const int nj2 = 2 * m.nj;
-        const int i0 = c.T.body_joint_start[b], n = c.T.body_joint_start[b + 1] - i0;
+        const int i0 = ROLE ? role.joint_start : c.T.body_joint_start[b], n = ROLE ? role.joint_count : c.T.body_joint_start[b + 1] - i0;
         struct Inc { vec3 lin, ang, t; };
         auto fetch = [&](int k) {
             Inc r;
@@ -881,7 +890,7 @@ NT_DI void apply_item(const Ctx<EPB>& c, const int b, const bool do_lin, const b
     if (want_lin) dp = dlin * (inv_m * weight);
     quat q1;
     if (do_ang) {
-        const mat33 inv_I = c.inv_inertia(b), body_I = c.inertia(b);
+        const mat33 inv_I = ROLE ? role_mat33(role.inv_inertia) : c.inv_inertia(b), body_I = ROLE ? role_mat33(role.inertia) : c.inertia(b);
         const quat q0 = c.body_rot(b);
         const vec3 w0 = c.body_w(b);
         vec3 dq = dang * weight;
@@ -900,7 +909,10 @@ NT_DI void apply_item(const Ctx<EPB>& c, const int b, const bool do_lin, const b
         // c.inv_inertia, velocity-from-delta the poses, report_parent_f the joint accumulators), and before the next step's solve
         // integrate_bodies rebuilds W from its own r1 for every body that reaches this line (a kernel entry: phase_body_derived).
         // W is never stored.  Kinematic and zero-mass bodies returned above and keep what those two wrote.
-        if (!(DEAD_W && last)) c.update_body_w(b, q1);
+        if (!(DEAD_W && last)) {
+            if constexpr (ROLE) c.update_body_w(b, q1, inv_I);
+            else c.update_body_w(b, q1);
+        }
     }
     if (do_lin) {
         vec3 v1 = c.body_v(b) + dp;
@@ -918,9 +930,10 @@ template <int EPB, bool FROM_CONTACTS, class CW = CwLds, bool FUSED = false, boo
 NT_DI void phase_apply(const Ctx<EPB>& c, const bool last) {
     if (!c.valid) return;
     const int nb = c.a.m.nb, S0 = body_lane_split(c);
+    constexpr bool ROLE = Ctx<EPB>::SPEC;  // (one trip per lane there: the lane's body is its role record's)
     if (Ctx<EPB>::SPEC || S0) {
-        if (c.slot < nb) apply_item<EPB, FROM_CONTACTS, CW, FUSED, ROWS, DEAD_W>(c, c.slot, false, true, last);
-        else if (c.slot >= S0 && c.slot < S0 + nb) apply_item<EPB, FROM_CONTACTS, CW, FUSED, ROWS, DEAD_W>(c, c.slot - S0, true, false, last);
+        if (c.slot < nb) apply_item<EPB, FROM_CONTACTS, CW, FUSED, ROWS, DEAD_W, ROLE>(c, c.slot, false, true, last);
+        else if (c.slot >= S0 && c.slot < S0 + nb) apply_item<EPB, FROM_CONTACTS, CW, FUSED, ROWS, DEAD_W, ROLE>(c, c.slot - S0, true, false, last);
     } else {
         for (int b = c.tslot; b < nb; b += c.nslot) apply_item<EPB, FROM_CONTACTS, CW, FUSED, ROWS, DEAD_W>(c, b, true, true, last);
     }
@@ -985,6 +998,38 @@ NT_DI bool joint_live(const Ctx<EPB>& c, int j, int& id_p, int& id_c, float& m_i
     m_inv_p = id_p >= 0 ? c.inv_mass(id_p) : 0.0f;
     m_inv_c = c.inv_mass(id_c);
     return !(m_inv_p == 0.0f && m_inv_c == 0.0f);
+}
+
+// ---- NT_SPEC lane roles (nt_ctx.hpp: BodyRole).  The loader reads what apply_item reads per call everywhere else, the same words from
+// the same tables, every load unconditional from an index clamped into its table.
+template <int EPB>
+NT_DI BodyRole load_body_role(const Ctx<EPB>& c, const int b) {
+    const nt_model& m = c.a.m;
+    const int nb = m.nb;
+    BodyRole r;
+    r.flags = c.T.body_flags[b];
+    r.inv_mass = c.inv_mass(b);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        r.inv_inertia[k] = c.pl(c.L.bp, BP_INV_INERTIA + k, nb, b);
+        r.inertia[k] = c.pl(c.L.bp, BP_INERTIA + k, nb, b);
+    }
+    r.pair_start = c.T.body_pair_start[b];
+    r.pair_count = c.T.body_pair_start[b + 1] - r.pair_start;
+    const int last = 2 * m.np - 1;  // (the table's allocated length: NT_TOPO_TABLE_LIST)
+    r.pair_code0 = c.T.body_pair_list[r.pair_start < 0 ? 0 : r.pair_start > last ? last : r.pair_start];
+    r.joint_start = c.T.body_joint_start[b];
+    r.joint_count = c.T.body_joint_start[b + 1] - r.joint_start;
+    return r;
+}
+// once per launch, behind the barriers that publish the topology region and the parameter copy and before the substep loop: slot s is
+// angular body s, slot B0 + s linear body s (phase_apply).  Lanes outside the two populations (slots [nb, B0) and from B0 + nb on), and
+// the lanes of worlds past env_count, fill from body 0 -- it exists: model_ok admits no model with nb == 0 -- and never read the result.
+template <int EPB>
+NT_DI void fill_lane_roles(Ctx<EPB>& c) {
+    static_assert(Ctx<EPB>::SPEC && Ctx<EPB>::UNI, "lane roles: the NT_SPEC instance (block-shared parameters: every lane reads in range)");
+    const int b = c.slot >= c.R.B0 ? c.slot - c.R.B0 : c.slot;
+    c.rb = load_body_role(c, b < c.a.m.nb ? b : 0);
 }
 
 template <int EPB>

@@ -252,7 +252,7 @@ __global__ void __launch_bounds__(THREADS, MINW) xpbd_rollout_kernel(KArgs a) {
     // pair-heavy tile: the substeps' contact records go through nt_contacts.cr, the Contacts buffers get the last substep's (the plain
     // position solve only: restitution reads the API layout)
     if constexpr (BIG) c.aos_records = a.ct.cr != nullptr && !xpbd_keeps_prestep_state(a.p);
-    const fused::Ctx<EPB> cf(c, 0);
+    fused::Ctx<EPB> cf(c, 0);
     const int nb = a.m.nb;
     load_tile(c, &a.s_in, true);  // (body_f is not staged: the rollout seeds body_f_tmp with the zeros clear_forces leaves)
     if constexpr (!Ctx<EPB>::SPEC) {  // (NT_SPEC: behind the substep loop)
@@ -268,6 +268,9 @@ __global__ void __launch_bounds__(THREADS, MINW) xpbd_rollout_kernel(KArgs a) {
     stage_global_world(c);  // (the topology tables it reads were published by the barrier above)
     c.gworld_ready = true;
     __syncthreads();
+    // NT_SPEC: every lane copies the launch-invariant operands of its body into registers (nt_ctx.hpp: lane roles).  The two barriers
+    // above have published what the copy reads -- the topology region, the parameter copy -- and no phase below stores to either.
+    if constexpr (Ctx<EPB>::SPEC) fused::fill_lane_roles(cf);
     NT_TICK(0);
     for (int s = 0; s < a.substeps; ++s) {
         c.hbm_out = !(c.lds_records || c.aos_records) || s == a.substeps - 1;
