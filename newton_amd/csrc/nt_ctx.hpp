@@ -32,6 +32,16 @@ struct BodyRole {  // the body of an angular lane [0, nb) or a linear lane [B0, 
     float inv_mass;
     float inv_inertia[9], inertia[9];
 };
+// ... and of a joint lane: slot j < nj is the linear lane of joint j, slot A0 + j its angular lane (phase_joints), one trip each
+// (xpbd_spec_tile_fits: wave_up(nj) + nj <= nslot).  What joint_live finds through four dependent LDS rounds, the two joint frames, the
+// dof starts and counts and the joint's two entries of the bodies' incidence lists.
+struct JointRole {
+    int type, enabled, id_p, id_c;    // T.joint_type / joint_enabled / joint_parent / joint_child [j]
+    float inv_mass_p, inv_mass_c;     // (a world-attached parent: 0, as joint_live has it)
+    float X_pj[7], X_cj[7];           // L.jp rows 0-6 and 7-13
+    int qd_start, tq_start, lin_count, ang_count;
+    int ip, ic;                       // T.joint_inc[2 j], [2 j + 1]
+};
 template <int EPB>
 struct Ctx {
     static constexpr int N = EPB & 255;
@@ -64,6 +74,7 @@ struct Ctx {
     struct Ranges { int B0, S0, I0, A0; } R;  // linear body lanes, joint-force lanes, integrate lanes, angular joint lanes
     // the lane's role (NT_SPEC only: fused::fill_lane_roles on the XPBD phases' context; never set, copied or read anywhere else)
     BodyRole rb;
+    JointRole rj;
 
     // rows: float rows per env in front of the block-shared topology ints (-1: the XPBD / collide layout)
     // defer_image: the kernel calls load_tile next (see issue_image)

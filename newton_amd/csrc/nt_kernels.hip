@@ -416,6 +416,7 @@ bool xpbd_spec_tile_fits(const KArgs& a, const XpbdCfg& c) {
     if (m.np > nslot || m.np > 64) return false;       // pairs_compacted() == false; one-level prefix (none runs on this tile)
     if (wave_up(m.np) + m.nb > nslot) return false;    // integrate_bodies beside the pairs: pose_in_off == L.xiq.off (overlap)
     if (wave_up(m.nb) + m.nb > nslot) return false;    // body_lane_split() != 0 (lane_split is the kernel's own compile-time fact)
+    if (wave_up(m.nj) + m.nj > nslot) return false;    // a joint lane makes one trip of phase_joints: its JointRole is its joint's
     return true;
 }
 

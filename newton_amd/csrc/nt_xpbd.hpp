@@ -1022,17 +1022,99 @@ NT_DI BodyRole load_body_role(const Ctx<EPB>& c, const int b) {
     r.joint_count = c.T.body_joint_start[b + 1] - r.joint_start;
     return r;
 }
+// ... and what the two joint items read per call (nt_ctx.hpp: JointRole).  The inverse masses as joint_live forms them: 0 for a
+// world-attached parent; the body indices of a joint that is never solved (disabled, FREE) are clamped into the table like the rest.
+template <int EPB>
+NT_DI JointRole load_joint_role(const Ctx<EPB>& c, const int j) {
+    const nt_model& m = c.a.m;
+    const int nj = m.nj, nb = m.nb;
+    auto in_table = [&](int b) { return b < 0 ? 0 : b >= nb ? nb - 1 : b; };
+    JointRole r;
+    r.type = c.T.joint_type[j];
+    r.enabled = c.T.joint_enabled[j];
+    r.id_p = c.T.joint_parent[j];
+    r.id_c = c.T.joint_child[j];
+    const float m_inv_p = c.inv_mass(in_table(r.id_p));
+    r.inv_mass_p = r.id_p >= 0 ? m_inv_p : 0.0f;
+    r.inv_mass_c = c.inv_mass(in_table(r.id_c));
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+        r.X_pj[k] = c.pl(c.L.jp, k, nj, j);
+        r.X_cj[k] = c.pl(c.L.jp, 7 + k, nj, j);
+    }
+    r.qd_start = c.T.joint_qd_start[j];
+    r.tq_start = c.T.joint_tq_start[j];
+    r.lin_count = c.T.joint_lin_count[j];
+    r.ang_count = c.T.joint_ang_count[j];
+    r.ip = c.T.joint_inc[2 * j];
+    r.ic = c.T.joint_inc[2 * j + 1];
+    return r;
+}
 // once per launch, behind the barriers that publish the topology region and the parameter copy and before the substep loop: slot s is
-// angular body s, slot B0 + s linear body s (phase_apply).  Lanes outside the two populations (slots [nb, B0) and from B0 + nb on), and
-// the lanes of worlds past env_count, fill from body 0 -- it exists: model_ok admits no model with nb == 0 -- and never read the result.
+// angular body s, slot B0 + s linear body s (phase_apply); slot s is the linear lane of joint s, slot A0 + s its angular lane
+// (phase_joints).  Lanes outside a population (slots [nb, B0) and from B0 + nb on; [nj, A0) and from A0 + nj on), and the lanes of worlds
+// past env_count, fill from body 0 / joint 0 -- they exist: model_ok admits no model with nb == 0, xpbd_spec_tile_fits none with
+// nj == 0 -- and never read the result.
 template <int EPB>
 NT_DI void fill_lane_roles(Ctx<EPB>& c) {
     static_assert(Ctx<EPB>::SPEC && Ctx<EPB>::UNI, "lane roles: the NT_SPEC instance (block-shared parameters: every lane reads in range)");
     const int b = c.slot >= c.R.B0 ? c.slot - c.R.B0 : c.slot;
     c.rb = load_body_role(c, b < c.a.m.nb ? b : 0);
+    const int j = c.slot >= c.R.A0 ? c.slot - c.R.A0 : c.slot;
+    c.rj = load_joint_role(c, j < c.a.m.nj ? j : 0);
 }
 
+// Measurement builds (tools/build_variant.py) switch the joint role per item and per group of fields, to find which of them moves a
+// result (profiles/joint_role_bisect.txt).  The product has all of it.
+#ifndef NT_JROLE_ITEMS
+#define NT_JROLE_ITEMS 3  // 1: joint_linear_item, 2: joint_angular_item
+#endif
+#ifndef NT_JROLE_FIELDS
+#define NT_JROLE_FIELDS 15  // 1: the joint_live group, 2: the two frames, 4: dof starts and counts, 8: the joint_inc tail
+#endif
+#ifndef NT_JROLE_OPAQUE
+#define NT_JROLE_OPAQUE 1
+#endif
+constexpr bool JR_LIVE = (NT_JROLE_FIELDS & 1) != 0, JR_FRAMES = (NT_JROLE_FIELDS & 2) != 0, JR_DOFS = (NT_JROLE_FIELDS & 4) != 0,
+               JR_INC = (NT_JROLE_FIELDS & 8) != 0;
+// A joint item reads every word of its record through role_read, AT the place where the generic item loads it.  The empty asm emits no
+// instruction; it makes the word a value defined per call inside the item's own block, as the load was, instead of one the optimiser
+// sees defined once in front of the substep loop.  Why: fp contract(fast) picks which product of a*b + c*d it fuses from the operand
+// order and use counts the mid-level passes leave, and those may change when a load becomes a loop-invariant register; an earlier joint
+// role left the generic instance by an ulp on the device.  With this record the plain read was bit-equal too in every variant tried
+// (profiles/joint_role_bisect.txt), so this is a precaution that keeps the items' blocks the generic ones', not a fix seen to be needed.
+NT_DI int role_read(int x) {
+#if NT_JROLE_OPAQUE && defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(x));
+#endif
+    return x;
+}
+NT_DI float role_read(float x) {
+#if NT_JROLE_OPAQUE && defined(__HIP_DEVICE_COMPILE__)
+    return __int_as_float(role_read(__float_as_int(x)));  // (its bit pattern: a plain 32-bit register either way)
+#else
+    return x;
+#endif
+}
+NT_DI xform role_xform(const float (&w)[7]) {
+    return xform(vec3(role_read(w[0]), role_read(w[1]), role_read(w[2])), quat(role_read(w[3]), role_read(w[4]), role_read(w[5]), role_read(w[6])));
+}
+// joint_live from the lane's record: the same tests on the same values
 template <int EPB>
+NT_DI bool joint_live_role(const Ctx<EPB>& c, int& id_p, int& id_c, float& m_inv_p, float& m_inv_c) {
+    const JointRole& r = c.rj;
+    const int type = role_read(r.type);
+    if (!role_read(r.enabled) || type == JT_FREE) return false;
+    id_c = role_read(r.id_c);
+    id_p = role_read(r.id_p);
+    m_inv_p = role_read(r.inv_mass_p);
+    m_inv_c = role_read(r.inv_mass_c);
+    return !(m_inv_p == 0.0f && m_inv_c == 0.0f);
+}
+
+// ROLE (NT_SPEC, whose joint lanes make one trip): j is the joint of the lane's role record c.rj, and what the item reads of the
+// block-shared tables per call comes from registers.  Same values, same arithmetic.
+template <int EPB, bool ROLE = false>
 NT_DI void joint_linear_item(const Ctx<EPB>& c, const int j) {
     const nt_model& m = c.a.m;
     const int nj = m.nj;
@@ -1041,10 +1123,11 @@ NT_DI void joint_linear_item(const Ctx<EPB>& c, const int j) {
     vec3 lin_delta_p, ang_delta_p, lin_delta_c, ang_delta_c;
     int id_p, id_c;
     float m_inv_p, m_inv_c;
-    if (joint_live(c, j, id_p, id_c, m_inv_p, m_inv_c)) {
-        const int type = c.T.joint_type[j];
-        xform X_pj = c.plxf(c.L.jp, 0, nj, j);
-        xform X_cj = c.plxf(c.L.jp, 7, nj, j);
+    const JointRole& role = c.rj;
+    if (ROLE && JR_LIVE ? joint_live_role(c, id_p, id_c, m_inv_p, m_inv_c) : joint_live(c, j, id_p, id_c, m_inv_p, m_inv_c)) {
+        const int type = ROLE && JR_LIVE ? role_read(role.type) : c.T.joint_type[j];
+        xform X_pj = ROLE && JR_FRAMES ? role_xform(role.X_pj) : c.plxf(c.L.jp, 0, nj, j);
+        xform X_cj = ROLE && JR_FRAMES ? role_xform(role.X_cj) : c.plxf(c.L.jp, 7, nj, j);
         xform X_wp = X_pj;
         vec3 world_com_p = X_pj.p;  // transform_point(pose_p = X_pj, com_p = 0) for world-attached joints
         vec3 vel_p(0.0f), omega_p(0.0f);
@@ -1071,9 +1154,9 @@ NT_DI void joint_linear_item(const Ctx<EPB>& c, const int j) {
         xform rel_pose = xform_inverse(X_wp) * X_wc;
         vec3 rel_p = rel_pose.p;
         vec3 x_p = X_wp.p, x_c = X_wc.p;
-        int axis_start = c.T.joint_qd_start[j];
-        int target_axis_start = c.T.joint_tq_start[j];
-        int lin_count = c.T.joint_lin_count[j];
+        int axis_start = ROLE && JR_DOFS ? role_read(role.qd_start) : c.T.joint_qd_start[j];
+        int target_axis_start = ROLE && JR_DOFS ? role_read(role.tq_start) : c.T.joint_tq_start[j];
+        int lin_count = ROLE && JR_DOFS ? role_read(role.lin_count) : c.T.joint_lin_count[j];
 
         if (type == JT_DISTANCE) {
             vec3 r_p = x_p - world_com_p, r_c = x_c - world_com_c;
@@ -1158,7 +1241,8 @@ NT_DI void joint_linear_item(const Ctx<EPB>& c, const int j) {
             lin_delta_p = -lin_c_sum;
         }
     }
-    const int ip = c.T.joint_inc[2 * j], ic = c.T.joint_inc[2 * j + 1];  // the (joint, side) entries of the two bodies' lists
+    // the (joint, side) entries of the two bodies' lists
+    const int ip = ROLE && JR_INC ? role_read(role.ip) : c.T.joint_inc[2 * j], ic = ROLE && JR_INC ? role_read(role.ic) : c.T.joint_inc[2 * j + 1];
     if (ip >= 0) {
         c.st_lv3(c.L.ji, 0, 2 * nj, ip, lin_delta_p);
         c.st_lv3(c.L.ji, 3, 2 * nj, ip, ang_delta_p);
@@ -1169,7 +1253,7 @@ NT_DI void joint_linear_item(const Ctx<EPB>& c, const int j) {
     }
 }
 
-template <int EPB>
+template <int EPB, bool ROLE = false>
 NT_DI void joint_angular_item(const Ctx<EPB>& c, const int j) {
     const nt_model& m = c.a.m;
     const int nj = m.nj;
@@ -1178,11 +1262,12 @@ NT_DI void joint_angular_item(const Ctx<EPB>& c, const int j) {
     vec3 t0, t1, t2;  // angular_c * d_lambda for the three angular rows (parent gets the negation); stored as their sum
     int id_p, id_c;
     float m_inv_p, m_inv_c;
-    const int type = c.T.joint_type[j];
+    const JointRole& role = c.rj;
+    const int type = ROLE && JR_LIVE ? role_read(role.type) : c.T.joint_type[j];
     bool angular_type = type == JT_FIXED || type == JT_PRISMATIC || type == JT_REVOLUTE || type == JT_D6;
-    if (angular_type && joint_live(c, j, id_p, id_c, m_inv_p, m_inv_c)) {
-        xform X_pj = c.plxf(c.L.jp, 0, nj, j);
-        xform X_cj = c.plxf(c.L.jp, 7, nj, j);
+    if (angular_type && (ROLE && JR_LIVE ? joint_live_role(c, id_p, id_c, m_inv_p, m_inv_c) : joint_live(c, j, id_p, id_c, m_inv_p, m_inv_c))) {
+        xform X_pj = ROLE && JR_FRAMES ? role_xform(role.X_pj) : c.plxf(c.L.jp, 0, nj, j);
+        xform X_cj = ROLE && JR_FRAMES ? role_xform(role.X_cj) : c.plxf(c.L.jp, 7, nj, j);
         quat q_p = X_pj.q;
         vec3 omega_p(0.0f);
         if (id_p >= 0) {
@@ -1191,9 +1276,10 @@ NT_DI void joint_angular_item(const Ctx<EPB>& c, const int j) {
         }
         quat q_c = c.body_rot(id_c) * X_cj.q;
         vec3 omega_c = c.body_w(id_c);
-        int axis_start = c.T.joint_qd_start[j];
-        int target_axis_start = c.T.joint_tq_start[j];
-        int lin_count = c.T.joint_lin_count[j], ang_count = c.T.joint_ang_count[j];
+        int axis_start = ROLE && JR_DOFS ? role_read(role.qd_start) : c.T.joint_qd_start[j];
+        int target_axis_start = ROLE && JR_DOFS ? role_read(role.tq_start) : c.T.joint_tq_start[j];
+        int lin_count = ROLE && JR_DOFS ? role_read(role.lin_count) : c.T.joint_lin_count[j];
+        int ang_count = ROLE && JR_DOFS ? role_read(role.ang_count) : c.T.joint_ang_count[j];
         typename Ctx<EPB>::Wsym W_p = c.w_tile(id_p >= 0 ? id_p : 0);  // (once, not per row)
         const typename Ctx<EPB>::Wsym W_c = c.w_tile(id_c);
         if (id_p < 0) W_p = typename Ctx<EPB>::Wsym{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
@@ -1270,7 +1356,7 @@ NT_DI void joint_angular_item(const Ctx<EPB>& c, const int j) {
         }
     }
     const vec3 t = (t0 + t1) + t2;  // (angular_p = -angular_c: the parent's entry gets the negation)
-    const int ip = c.T.joint_inc[2 * j], ic = c.T.joint_inc[2 * j + 1];
+    const int ip = ROLE && JR_INC ? role_read(role.ip) : c.T.joint_inc[2 * j], ic = ROLE && JR_INC ? role_read(role.ic) : c.T.joint_inc[2 * j + 1];
     if (ip >= 0) c.st_lv3(c.L.ji, 6, 2 * nj, ip, -t);
     if (ic >= 0) c.st_lv3(c.L.ji, 6, 2 * nj, ic, t);
 }
@@ -1608,9 +1694,11 @@ NT_DI void phase_joints(const Ctx<EPB>& c) {
     const int spw = 64 / Ctx<EPB>::N > 0 ? 64 / Ctx<EPB>::N : 1;
     const int A0 = Ctx<EPB>::SPEC ? c.R.A0 : ((nj + spw - 1) / spw) * spw;
     NT_SKIP_DECL(c.a);  // (measurement builds: 32 skips the linear-row lanes, 64 the angular-row lanes)
+    // (NT_SPEC: one trip -- xpbd_spec_tile_fits: wave_up(nj) + nj <= nslot -- so i is the lane's slot and the joint its role record's)
+    constexpr bool ROLE_LIN = Ctx<EPB>::SPEC && (NT_JROLE_ITEMS & 1) != 0, ROLE_ANG = Ctx<EPB>::SPEC && (NT_JROLE_ITEMS & 2) != 0;
     for (int i = c.slot; i < A0 + nj; i += c.nslot) {
-        if (i < nj) { if (!NT_SKIP(32)) joint_linear_item(c, i); }
-        else if (i >= A0) { if (!NT_SKIP(64)) joint_angular_item(c, i - A0); }
+        if (i < nj) { if (!NT_SKIP(32)) joint_linear_item<EPB, ROLE_LIN>(c, i); }
+        else if (i >= A0) { if (!NT_SKIP(64)) joint_angular_item<EPB, ROLE_ANG>(c, i - A0); }
     }
 }
 
