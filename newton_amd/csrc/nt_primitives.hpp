@@ -3,6 +3,9 @@
 // and the dispatch order of narrow_phase_primitive_kernel (newton/_src/geometry/narrow_phase.py:642-865).
 // Normal points from shape A into shape B; position is the midpoint between the surfaces; distance < 0 is
 // penetration; unused contact slots carry NT_MAXVAL.
+// Two deliberate deviations from the reference's numbers, each described at its function and in DESIGN.md section 3.1a: capsule_capsule
+// (the exact closest pair of the two segments; the reference's is wrong for parallel and nearly parallel axes) and plane_ellipsoid (the
+// distance from the support function: same value, less rounding).
 #pragma once
 #include "nt_math.hpp"
 
@@ -66,6 +69,28 @@ NT_DI void sphere_sphere(vec3 p1, float r1, vec3 p2, float r2, float& dist, vec3
     pos = p1 + n * (r1 + 0.5f * dist);
 }
 
+// sin^2 of the angle between two capsule axes below which the pair counts as parallel (an angle of 3.2e-6 rad): 100 times the float32
+// rounding of |axis1 x axis2|^2 for identical axes, and small enough that the two contacts at the ends of the overlap miss the exact
+// closest approach of skew axes by less than one float32 ulp of the capsule length
+constexpr float NT_CAPSULE_PARALLEL = 1e-11f;
+// sin^2 of the angle (30 degrees) from which on the reference's arithmetic is kept to the bit: det = ma * mc - mb * mb has lost 2 bits there
+constexpr float NT_CAPSULE_LITERAL = 0.25f;
+
+// DELIBERATE DEVIATION from the reference (collision_primitive.py:180-275, a float32 port of a double-precision routine whose branch
+// test `abs(det) >= 1e-15` on det = ma * mc - mb * mb is rounding noise for parallel axes, and whose parallel branch only projects
+// capsule 1's end points): for axes less than 30 degrees apart the result is the exact closest pair of the two segments.
+//   * det = |axis1 x axis2|^2 and the numerator (axis1 x axis2) . (dif x axis2) are the same quantities without the cancellation
+//     (Lagrange / Binet-Cauchy identities); the parallel decision is relative to ma * mc.
+//   * whatever parameter x1 is chosen on segment 1, x2 is its re-projected, clamped closest point on segment 2 and x1 is then
+//     re-projected from x2 (capsule_refine): the two points are always each other's closest points, so an ill-conditioned x1 costs
+//     second order only, and a capsule 1 that overhangs capsule 2 gets the interior point across capsule 2's end.
+//   * parallel axes: one contact from each end of capsule 1 (the two ends of the overlap); a second contact equal to the first
+//     (no overlap: both collapse onto the same pair of end points) is dropped.  Never more than 2 contacts.
+NT_DI void capsule_refine(float x1, float ma, float mb, float mc, float u, float v, float& x1o, float& x2o) {
+    x2o = clampf((v - mb * x1) / mc, -1.0f, 1.0f);
+    x1o = clampf((u - mb * x2o) / ma, -1.0f, 1.0f);
+}
+
 NT_DI void capsule_capsule(vec3 c1, vec3 ax1, float r1, float h1, vec3 c2, vec3 ax2, float r2, float h2, Contacts4& out) {
     vec3 axis1 = ax1 * h1;
     vec3 axis2 = ax2 * h2;
@@ -75,35 +100,41 @@ NT_DI void capsule_capsule(vec3 c1, vec3 ax1, float r1, float h1, vec3 c2, vec3 
     float mc = dot(axis2, axis2);
     float u = -dot(axis1, dif);
     float v = dot(axis2, dif);
-    float det = ma * mc - mb * mb;
-    if (fabsf(det) >= NT_MINVAL) {
-        float inv_det = 1.0f / det;
-        float x1 = (mc * u - mb * v) * inv_det;
-        float x2 = (ma * v - mb * u) * inv_det;
+    vec3 cr = cross(axis1, axis2);
+    float det = dot(cr, cr);
+    bool parallel = det <= NT_CAPSULE_PARALLEL * (ma * mc);
+    float x1, x2;
+    if (det >= NT_CAPSULE_LITERAL * (ma * mc)) {
+        // axes more than 30 degrees apart: the reference's own arithmetic, to the bit (exact in exact arithmetic and a few ulps off in
+        // float32 there; the executed-reference fixtures, which are compared bit for bit after a solver step, stay as they are)
+        float inv_det = 1.0f / (ma * mc - mb * mb);
+        x1 = (mc * u - mb * v) * inv_det;
+        x2 = (ma * v - mb * u) * inv_det;
         if (x1 > 1.0f) { x1 = 1.0f; x2 = (v - mb) / mc; }
         else if (x1 < -1.0f) { x1 = -1.0f; x2 = (v + mb) / mc; }
         if (x2 > 1.0f) { x2 = 1.0f; x1 = clampf((u - mb) / ma, -1.0f, 1.0f); }
         else if (x2 < -1.0f) { x2 = -1.0f; x1 = clampf((u + mb) / ma, -1.0f, 1.0f); }
-        vec3 v1 = c1 + axis1 * x1;
-        vec3 v2 = c2 + axis2 * x2;
-        sphere_sphere(v1, r1, v2, r2, out.d0, out.p0, out.normal);
     } else {
-        vec3 v1 = c1 + axis1;
-        float x2 = clampf((v - mb) / mc, -1.0f, 1.0f);
-        vec3 v2 = c2 + axis2 * x2;
-        sphere_sphere(v1, r1, v2, r2, out.d0, out.p0, out.normal);
-        v1 = c1 - axis1;
-        x2 = clampf((v + mb) / mc, -1.0f, 1.0f);
-        v2 = c2 + axis2 * x2;
+        capsule_refine(parallel ? 1.0f : clampf(-dot(cr, cross(dif, axis2)) / det, -1.0f, 1.0f), ma, mb, mc, u, v, x1, x2);
+    }
+    sphere_sphere(c1 + axis1 * x1, r1, c2 + axis2 * x2, r2, out.d0, out.p0, out.normal);
+    if (parallel) {
+        float y1, y2, d1;
         vec3 n_unused;
-        sphere_sphere(v1, r1, v2, r2, out.d1, out.p1, n_unused);
+        capsule_refine(-1.0f, ma, mb, mc, u, v, y1, y2);
+        sphere_sphere(c1 + axis1 * y1, r1, c2 + axis2 * y2, r2, d1, out.p1, n_unused);
+        out.d1 = (y1 == x1 && y2 == x2) ? NT_MAXVAL : d1;
     }
 }
 
 NT_DI void plane_ellipsoid(vec3 n, vec3 plane_pos, vec3 c, const mat33& rot, vec3 size, Contacts4& out) {
-    vec3 s = -normalize(cw_mul(transpose(rot) * n, size));
-    vec3 pos = c + rot * cw_mul(s, size);
-    float dist = dot(n, pos - plane_pos);
+    // the support point of the ellipsoid against the plane normal.  The distance is the centre's height minus the support function
+    // h(n) = |size * (R^T n)| -- the reference's n . (support point - plane_pos) in exact arithmetic, without the rounding of a point
+    // rotated into the world and projected back (worst exported distance on a 1 m ellipsoid: 2.3 float32 ulps of its size before, 1.7 now)
+    vec3 sn = cw_mul(transpose(rot) * n, size);
+    float h = length(sn);
+    vec3 pos = c - rot * cw_mul(sn / h, size);
+    float dist = dot(n, c - plane_pos) - h;
     pos = pos - n * dist * 0.5f;
     out.d0 = dist;
     out.p0 = pos;

@@ -34,7 +34,8 @@ struct mat43f {
     vec3 r[4];
 };
 
-static const float MINVAL = 1e-15f;
+static const float CAPSULE_PARALLEL = 1e-11f;  // NT_CAPSULE_PARALLEL of nt_primitives.hpp
+static const float CAPSULE_LITERAL = 0.25f;    // NT_CAPSULE_LITERAL
 
 // ---------------------------------------------------------------- collision_primitive.py:48-98
 static vec3 closest_segment_point(vec3 a, vec3 b, vec3 pt) {
@@ -87,13 +88,21 @@ static void collide_capsule_capsule(vec3 cap1_pos, vec3 cap1_axis, float cap1_ra
     float mc = dot(axis2, axis2);
     float u = -dot(axis1, dif);
     float v = dot(axis2, dif);
-    float det = ma * mc - mb * mb;
-
-    if (std::fabs(det) >= MINVAL) {
-        float inv_det = 1.0f / det;
-        float x1 = (mc * u - mb * v) * inv_det;
-        float x2 = (ma * v - mb * u) * inv_det;
-
+    // DELIBERATE DEVIATION from collision_primitive.py:180-275, restating capsule_capsule of newton_amd/csrc/nt_primitives.hpp (see the
+    // comment there): det and the numerator of x1 through cross products, the parallel decision relative to ma * mc, every chosen
+    // parameter re-projected onto the other segment and back, a duplicate second contact dropped
+    vec3 cr = cross(axis1, axis2);
+    float det = dot(cr, cr);
+    bool parallel = det <= CAPSULE_PARALLEL * (ma * mc);
+    auto refine = [&](float x1, float& x1o, float& x2o) {
+        x2o = clampf((v - mb * x1) / mc, -1.0f, 1.0f);
+        x1o = clampf((u - mb * x2o) / ma, -1.0f, 1.0f);
+    };
+    float x1, x2;
+    if (det >= CAPSULE_LITERAL * (ma * mc)) {  // more than 30 degrees apart: the reference's arithmetic, to the bit
+        float inv_det = 1.0f / (ma * mc - mb * mb);
+        x1 = (mc * u - mb * v) * inv_det;
+        x2 = (ma * v - mb * u) * inv_det;
         if (x1 > 1.0f) {
             x1 = 1.0f;
             x2 = (v - mb) / mc;
@@ -108,29 +117,28 @@ static void collide_capsule_capsule(vec3 cap1_pos, vec3 cap1_axis, float cap1_ra
             x2 = -1.0f;
             x1 = clampf((u + mb) / ma, -1.0f, 1.0f);
         }
-        vec3 vec1 = cap1_pos + axis1 * x1;
-        vec3 vec2 = cap2_pos + axis2 * x2;
-        collide_sphere_sphere(vec1, cap1_radius, vec2, cap2_radius, contact_dist[0], contact_pos[0], contact_normal);
     } else {
-        vec3 vec1 = cap1_pos + axis1;
-        float x2 = clampf((v - mb) / mc, -1.0f, 1.0f);
-        vec3 vec2 = cap2_pos + axis2 * x2;
-        collide_sphere_sphere(vec1, cap1_radius, vec2, cap2_radius, contact_dist[0], contact_pos[0], contact_normal);
-
-        vec1 = cap1_pos - axis1;
-        x2 = clampf((v + mb) / mc, -1.0f, 1.0f);
-        vec2 = cap2_pos + axis2 * x2;
+        refine(parallel ? 1.0f : clampf(-dot(cr, cross(dif, axis2)) / det, -1.0f, 1.0f), x1, x2);
+    }
+    collide_sphere_sphere(cap1_pos + axis1 * x1, cap1_radius, cap2_pos + axis2 * x2, cap2_radius, contact_dist[0], contact_pos[0],
+                          contact_normal);
+    if (parallel) {
+        float y1, y2, d1;
         vec3 n_unused;
-        collide_sphere_sphere(vec1, cap1_radius, vec2, cap2_radius, contact_dist[1], contact_pos[1], n_unused);
+        refine(-1.0f, y1, y2);
+        collide_sphere_sphere(cap1_pos + axis1 * y1, cap1_radius, cap2_pos + axis2 * y2, cap2_radius, d1, contact_pos[1], n_unused);
+        contact_dist[1] = (y1 == x1 && y2 == x2) ? MAXVAL : d1;
     }
 }
 
 // collision_primitive.py:352-381
 static void collide_plane_ellipsoid(vec3 plane_normal, vec3 plane_pos, vec3 ellipsoid_pos, const mat33& ellipsoid_rot,
                                     vec3 ellipsoid_size, float& dist, vec3& pos, vec3& normal) {
-    vec3 sphere_support = -normalize(cw_mul(transpose(ellipsoid_rot) * plane_normal, ellipsoid_size));
-    pos = ellipsoid_pos + ellipsoid_rot * cw_mul(sphere_support, ellipsoid_size);
-    dist = dot(plane_normal, pos - plane_pos);
+    // (restating plane_ellipsoid of nt_primitives.hpp: the distance through the support function h(n) = |size * (R^T n)|)
+    vec3 sn = cw_mul(transpose(ellipsoid_rot) * plane_normal, ellipsoid_size);
+    float h = length(sn);
+    pos = ellipsoid_pos - ellipsoid_rot * cw_mul(sn / h, ellipsoid_size);
+    dist = dot(plane_normal, ellipsoid_pos - plane_pos) - h;
     pos = pos - plane_normal * dist * 0.5f;
     normal = plane_normal;
 }

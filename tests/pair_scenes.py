@@ -21,9 +21,11 @@ def pair_model(geoms, device=None):
 def decode_world(model, body_q, shape0, shape1, point0, point1, normal, margin0, margin1):
     """-> list of (center, normal, penetration) like the reference test writer (penetration = distance - margins)."""
     out = []
+    world = nm.transform_identity()  # a static shape (body -1) keeps its points in the world frame
     for i in range(len(shape0)):
-        X0 = body_q[model.shape_body[shape0[i]]]
-        X1 = body_q[model.shape_body[shape1[i]]]
+        b0, b1 = model.shape_body[shape0[i]], model.shape_body[shape1[i]]
+        X0 = body_q[b0] if b0 >= 0 else world
+        X1 = body_q[b1] if b1 >= 0 else world
         p0 = nm.transform_point(X0, point0[i])
         p1 = nm.transform_point(X1, point1[i])
         n = np.asarray(normal[i], dtype=np.float64)
