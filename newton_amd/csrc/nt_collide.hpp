@@ -216,7 +216,7 @@ NT_DI void write_contact_slot(const Ctx<EPB>& c, int slot, int sa, int sb, vec3 
     vec3 bw = center + n * (0.5f * dist + rb);
     vec3 p0 = xform_point(Xbw_a, aw), p1 = xform_point(Xbw_b, bw);
     vec3 o0 = xform_vector(Xbw_a, off_a * n), o1 = xform_vector(Xbw_b, -off_b * n);
-    if (c.big && c.aos_records) {  // the pair-heavy rollout's own copy: one line per slot, read back by its contact phases
+    if (c.is_big() && c.has_aos_records()) {  // the pair-heavy rollout's own copy: one line per slot, read back by its contact phases
         float* o = ct.cr + ((size_t)c.env * ncs + slot) * NT_CR_STRIDE;
         o[CD_POINT0] = p0.x; o[CD_POINT0 + 1] = p0.y; o[CD_POINT0 + 2] = p0.z;
         o[CD_POINT1] = p1.x; o[CD_POINT1 + 1] = p1.y; o[CD_POINT1 + 2] = p1.z;
@@ -346,7 +346,7 @@ NT_DI void pair_eval_item(const Ctx<EPB>& c, const int p) {
                 nvalid += ok ? 1 : 0;
             }
             if constexpr (!STAGED)
-                for (int i = nvalid; (!c.big || c.hbm_out) && i < cpp; ++i) {
+                for (int i = nvalid; (!c.is_big() || c.hbm_out) && i < cpp; ++i) {
                     size_t gi = (size_t)(p * cpp + i) * c.ES + c.env;
                     ct.shape0[gi] = -1;
                     ct.shape1[gi] = -1;
@@ -370,7 +370,7 @@ NT_DI void pair_eval_item(const Ctx<EPB>& c, const int p) {
                     write_contact_slot(c, p * cpp + nvalid, sa, sb, center, n, dist, 0.0f, 0.0f, margin_a, margin_b);
                     nvalid += 1;
                 }
-                for (int i = nvalid; (!c.big || c.hbm_out) && i < cpp; ++i) {
+                for (int i = nvalid; (!c.is_big() || c.hbm_out) && i < cpp; ++i) {
                     size_t gi = (size_t)(p * cpp + i) * c.ES + c.env;
                     ct.shape0[gi] = -1;
                     ct.shape1[gi] = -1;
@@ -398,7 +398,7 @@ NT_DI void pair_eval_item(const Ctx<EPB>& c, const int p) {
                                         vmax(cw_mul(vec3(mb[0], mb[1], mb[2]), scale_b), cw_mul(vec3(mb[3], mb[4], mb[5]), scale_b)));
                 }
                 PolyRef poly;  // manifold polygon scratch: per convex pair, or (pair-heavy tile) per lane
-                poly.base = &c.lds[(c.L.poly + 20 * (c.big ? c.slot : p - m.np_analytic)) * Ctx<EPB>::N + c.e];
+                poly.base = &c.lds[(c.L.poly + 20 * (c.is_big() ? c.slot : p - m.np_analytic)) * Ctx<EPB>::N + c.e];
                 poly.stride = Ctx<EPB>::N;
                 convex_pair(ga, gb, Xa, Xb, margin_a, margin_b, gap_sum, lob, hib, poly, cc);
                 float ra = (ta == GEO_SPHERE || ta == GEO_CAPSULE) ? scale_a.x : 0.0f;
@@ -408,7 +408,7 @@ NT_DI void pair_eval_item(const Ctx<EPB>& c, const int p) {
                 for (int i = 0; i < cpp; ++i) {
                     if (i < nvalid) {
                         write_contact_slot(c, p * cpp + i, sa, sb, cc.center(i), n, cc.distance(i), ra, rb, margin_a, margin_b);
-                    } else if (!c.big || c.hbm_out) {
+                    } else if (!c.is_big() || c.hbm_out) {
                         size_t gi = (size_t)(p * cpp + i) * c.ES + c.env;
                         ct.shape0[gi] = -1;
                         ct.shape1[gi] = -1;
@@ -425,7 +425,7 @@ NT_DI void pair_eval_item(const Ctx<EPB>& c, const int p) {
     }
     c.l(c.L.pc, 0, m.np, p) = (float)nvalid;
     c.l(c.L.pm, 0, m.np, p) = (float)nvalid;
-    if (STAGED && c.lds_records && nvalid > 0) {
+    if (STAGED && c.has_lds_records() && nvalid > 0) {
         // LDS-record tiles: the pair lane appends its live contacts to the environment's list itself (one LDS atomic), so no prefix
         // pass exists.  The ORDER of the list varies with the waves' timing and does not matter: every contact owns its slot's record
         // (L.cr / L.cw) and the body lanes sum in slot order.
@@ -603,7 +603,7 @@ NT_DI void phase_pair_eval(const Ctx<EPB>& c) {
 template <int EPB>
 NT_DI bool pairs_compacted(const Ctx<EPB>& c) {
     if constexpr (Ctx<EPB>::SPEC) return false;  // (np <= nslot: verified by the launch code)
-    else return !c.big && c.a.m.np > c.nslot;
+    else return !c.is_big() && c.a.m.np > c.nslot;
 }
 template <int EPB>
 NT_DI void phase_pair_broad_staged(const Ctx<EPB>& c) {
@@ -675,7 +675,7 @@ NT_DI void prefix_lane(const Ctx<EPB>& c, int lane, int partial, bool store_env_
     for (int p = lane * chunk; p < np && p < (lane + 1) * chunk; ++p) {
         c.l(c.L.px, 0, 1, p) = (float)acc;
         const int live = (int)c.l(c.L.pm, 0, np, p);
-        if (c.L.has_lt)  // the compacted live-contact list of the fused contact phases (entry: pair << 4 | sub-contact)
+        if (c.has_live_list())  // the compacted live-contact list of the fused contact phases (entry: pair << 4 | sub-contact)
             for (int k = 0; k < live; ++k) *reinterpret_cast<int*>(&c.l(c.L.lt, 0, 1, acc + k)) = (p << 4) | k;
         acc += live;
     }

@@ -67,6 +67,12 @@ struct Ctx {
     bool aos_records;  // pair-heavy fused rollout: the substep's contact records live in nt_contacts.cr (one line per slot); hbm_out then
                        // only holds for the last substep
     bool big;  // contact records in HBM, manifold polygon scratch per lane (compile-time constant at every construction site)
+    // The flags above that xpbd_spec_tile_fits fixes, as the phases ask for them: constants on the NT_SPEC instance (records and live
+    // list in LDS, a staged tile), the members everywhere else.  hbm_out changes inside a launch and stays a plain member.
+    NT_DI bool has_lds_records() const { if constexpr (SPEC) return true; else return lds_records; }
+    NT_DI bool has_aos_records() const { if constexpr (SPEC) return false; else return aos_records; }
+    NT_DI bool is_big() const { if constexpr (SPEC) return false; else return big; }
+    NT_DI bool has_live_list() const { if constexpr (SPEC) return true; else return L.has_lt != 0; }
     int ES;
     bool valid;
     // launch-invariant slot ranges (first slot of the second population of a shared interval, on a wave boundary), computed once here

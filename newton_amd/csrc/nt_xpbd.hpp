@@ -618,8 +618,16 @@ NT_DI LoadedRecord make_lds_record(const Ctx<EPB>& c, int slot, int shape_a, int
     L.m = r[CD_MARGIN0] + r[CD_MARGIN1];
     return L;
 }
-template <int EPB, bool FUSED, class CW = CwLds>
+// LISTED (the NT_SPEC call site of phase_contacts): every contact the lane takes comes from the compacted list with its pair
+// (live_pair >= 0) and its record is in L.cr, so the instance is compiled with the first two branches below and nothing else -- no
+// record reload from HBM, no slot / cpp, no pair -> shape -> body lookups, no pair_a comparison.
+// Measurement builds (tools/build_variant.py) switch it off with -DNT_SPEC_LISTED=0; the product has it.
+#ifndef NT_SPEC_LISTED
+#define NT_SPEC_LISTED 1
+#endif
+template <int EPB, bool FUSED, class CW = CwLds, bool LISTED = false>
 NT_DI void contact_item(const Ctx<EPB>& c, const int slot, const int live_pair = -1, const bool make_record = false) {
+    static_assert(!LISTED || (Ctx<EPB>::SPEC && FUSED), "a listed and described contact: the NT_SPEC instance of the fused rollout");
     const nt_model& m = c.a.m;
     const nt_contacts& ct = c.a.ct;
     const int cpp = m.cpp, ncs = m.np * cpp;
@@ -630,7 +638,7 @@ NT_DI void contact_item(const Ctx<EPB>& c, const int slot, const int live_pair =
     int shape_a = -1, shape_b = -1, body_a = -1, body_b = -1;
     bool swapped = false, described = false;
     LoadedRecord rec;
-    if (Ctx<EPB>::SPEC && FUSED && live_pair >= 0 && make_record) {  // (the descriptor first: the conversion needs it)
+    if (Ctx<EPB>::SPEC && FUSED && (LISTED || live_pair >= 0) && make_record) {  // (the descriptor first: the conversion needs it)
         const int* d = c.T.pair_desc + 4 * live_pair;
         shape_a = d[0]; shape_b = d[1]; body_a = d[2];
         const int w = d[3];
@@ -639,8 +647,8 @@ NT_DI void contact_item(const Ctx<EPB>& c, const int slot, const int live_pair =
         live = body_a != body_b;
         described = true;
         if constexpr (Ctx<EPB>::SPEC) rec = make_lds_record(c, slot, shape_a, shape_b, body_a, body_b);
-    } else if (FUSED && live_pair >= 0) {
-        if (c.lds_records) rec = load_record(LdsRecord<EPB>{c, ncs, slot});
+    } else if (FUSED && (LISTED || live_pair >= 0)) {
+        if (c.has_lds_records()) rec = load_record(LdsRecord<EPB>{c, ncs, slot});
         else rec = load_record(SlotRecord<EPB>{c, ct.data, ncs, slot});  // (a listed contact is live: fetch before anything depends on LDS)
         const int* d = c.T.pair_desc + 4 * live_pair;
         shape_a = d[0]; shape_b = d[1]; body_a = d[2];
@@ -649,6 +657,8 @@ NT_DI void contact_item(const Ctx<EPB>& c, const int slot, const int live_pair =
         body_b = (w << 2) >> 2;  // sign-extend the 30-bit body index
         live = body_a != body_b;
         described = true;
+    } else if constexpr (LISTED) {
+        live = false;  // (never reached: one of the two branches above is taken)
     } else if (FUSED) {
         const int p = slot / cpp, k = slot - p * cpp;
         live = k < (int)c.l(c.L.pm, 0, m.np, p);
@@ -668,20 +678,22 @@ NT_DI void contact_item(const Ctx<EPB>& c, const int slot, const int live_pair =
             shape_b = gid_b >= 0 ? c.local_shape_id(gid_b) : -1;
         }
     }
-    if (live && !described) {
-        body_a = shape_a >= 0 ? c.T.shape_body[shape_a] : -1;
-        body_b = shape_b >= 0 ? c.T.shape_body[shape_b] : -1;
-        live = body_a != body_b;
-    }
-    if (live && !described) {
-        if (FUSED && c.big && c.aos_records) rec = load_record(AosRecord<EPB>{ct.cr + ((size_t)c.env * ncs + slot) * NT_CR_STRIDE});
-        else rec = load_record(SlotRecord<EPB>{c, ct.data, ncs, slot});
+    if constexpr (!LISTED) {
+        if (live && !described) {
+            body_a = shape_a >= 0 ? c.T.shape_body[shape_a] : -1;
+            body_b = shape_b >= 0 ? c.T.shape_body[shape_b] : -1;
+            live = body_a != body_b;
+        }
+        if (live && !described) {
+            if (FUSED && c.is_big() && c.has_aos_records()) rec = load_record(AosRecord<EPB>{ct.cr + ((size_t)c.env * ncs + slot) * NT_CR_STRIDE});
+            else rec = load_record(SlotRecord<EPB>{c, ct.data, ncs, slot});
+        }
     }
     if (live && contact_solve(c, rec, shape_a, shape_b, body_a, body_b, lin_delta_a, ang_delta_a, ang_delta_b,
                               !FUSED && c.a.rep.contact_impulse != nullptr)) {
         has_a = body_a >= 0 ? 1.0f : 0.0f;
         has_b = body_b >= 0 ? 1.0f : 0.0f;
-        if (described) a_is_pair_a = swapped ? 0.0f : 1.0f;
+        if (LISTED || described) a_is_pair_a = swapped ? 0.0f : 1.0f;
         else a_is_pair_a = (shape_a == c.T.pair_a[slot / cpp]) ? 1.0f : 0.0f;
     }
     // lin_delta_b == -lin_delta_a bit for bit (IEEE negation commutes with every rounding above), so only one is stored
@@ -734,10 +746,10 @@ NT_DI void phase_contacts(const Ctx<EPB>& c, const bool make_record = false) {
         // of dead slots are never written and never read (apply_item stops at the pair's live count)
         // (NT_SPEC: the count the pair lanes left in L.lc -- no prefix runs on that tile; make_record: see contact_item)
         const int total = Ctx<EPB>::SPEC ? *reinterpret_cast<const int*>(&c.l(c.L.lc, 0, 1, 0)) : (int)c.l(c.L.px, 0, 1, np);
-        if (c.L.has_lt) {  // the compacted list written with the prefix: no search
+        if (c.has_live_list()) {  // the compacted list written with the prefix: no search
             for (int i = c.tslot; i < total; i += c.nslot) {
                 const int e = *reinterpret_cast<const int*>(&c.l(c.L.lt, 0, 1, i));
-                contact_item<EPB, FUSED, CW>(c, (e >> 4) * cpp + (e & 15), e >> 4, make_record);
+                contact_item<EPB, FUSED, CW, Ctx<EPB>::SPEC && NT_SPEC_LISTED != 0>(c, (e >> 4) * cpp + (e & 15), e >> 4, make_record);
             }
         } else {
             for (int i = c.tslot; i < total; i += c.nslot) {

@@ -14,7 +14,7 @@ NT_DI void do_collide(const Ctx<EPB>& c, bool count_contacts) {
     phase_shapes(c);
     __syncthreads();
     NT_TICK(1);
-    if (c.big) {
+    if (c.is_big()) {
         phase_pairs_big_broad(c);  // pair-heavy tile: compact the candidates first, no candidate staging (19 rows per pair)
         phase_pairs_big_narrow<EPB, CVX>(c);
     } else {
@@ -77,7 +77,7 @@ NT_DI void do_fused_substep(const Ctx<EPB>& c, const fused::Ctx<EPB>& cf, bool l
     const bool snapshot_copy = !SPEC && (restitution || overlap);
     if (c.valid) {
         if (compact && c.slot == 0) *reinterpret_cast<int*>(&c.l(c.L.hc, 0, 1, 0)) = 0;
-        if (c.lds_records && c.slot == 0) *reinterpret_cast<int*>(&c.l(c.L.lc, 0, 1, 0)) = 0;
+        if (c.has_lds_records() && c.slot == 0) *reinterpret_cast<int*>(&c.l(c.L.lc, 0, 1, 0)) = 0;
         if (snapshot_copy)
             for (int r = c.slot; r < (restitution ? 14 : 7) * m.nb; r += c.nslot) c.lds[(c.L.xiq.off + r) * Ctx<EPB>::N + c.e] = c.lds[(c.L.bq.off + r) * Ctx<EPB>::N + c.e];
         if (!NT_SKIP(2)) fused::seed_body_forces(cf, true);
@@ -116,7 +116,7 @@ NT_DI void do_fused_substep(const Ctx<EPB>& c, const fused::Ctx<EPB>& cf, bool l
     // are parked in L.cr and not in L.st: no lane reads the union here, so no lane's L.cw store can reach a row another wave still
     // needs.  The list order (L.lt) varies with the waves' timing and decides nothing: every slot has one owner and one record.
     if constexpr (!SPEC) {
-        if (!NT_SKIP(1) && c.valid && c.lds_records) {
+        if (!NT_SKIP(1) && c.valid && c.has_lds_records()) {
             // LDS-record tiles: one lane per LIVE contact (the pair lanes built the list), records into L.cr
             const int total = *reinterpret_cast<const int*>(&c.l(c.L.lc, 0, 1, 0));
             for (int i = c.slot; i < total; i += c.nslot) contact_record_item_lds(c, *reinterpret_cast<const int*>(&c.l(c.L.lt, 0, 1, i)));
@@ -139,11 +139,11 @@ NT_DI void do_fused_substep(const Ctx<EPB>& c, const fused::Ctx<EPB>& cf, bool l
             }
         }
         __syncthreads();  // also publishes the contact records (global memory) to the block's contact lanes
-        if (!NT_SKIP(1) && m.np > 64 && !c.lds_records) {
+        if (!NT_SKIP(1) && m.np > 64 && !c.has_lds_records()) {
             phase_pair_prefix_scan(c, c.L.sx.off, last_substep, false);
             __syncthreads();
         }
-        if (c.lds_records && last_substep && c.valid)  // the launch's Contacts output (reads L.cr / L.pm only: no barrier needed behind it)
+        if (c.has_lds_records() && last_substep && c.valid)  // the launch's Contacts output (reads L.cr / L.pm only: no barrier needed behind it)
             for (int s = c.slot; s < m.np * m.cpp; s += c.nslot) contact_export_item_lds(c, s);
     }
     NT_TICK(3);
@@ -273,7 +273,7 @@ __global__ void __launch_bounds__(THREADS, MINW) xpbd_rollout_kernel(KArgs a) {
     if constexpr (Ctx<EPB>::SPEC) fused::fill_lane_roles(cf);
     NT_TICK(0);
     for (int s = 0; s < a.substeps; ++s) {
-        c.hbm_out = !(c.lds_records || c.aos_records) || s == a.substeps - 1;
+        c.hbm_out = !(c.has_lds_records() || c.has_aos_records()) || s == a.substeps - 1;
         if constexpr (BIG) {
             do_collide<EPB, CVX>(c, s == a.substeps - 1);
             fused::do_xpbd_step<EPB, true, fused::CwHbm>(cf, true);
